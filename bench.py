@@ -7,9 +7,11 @@ column packs of the chunks are resident in HBM before the timed region starts.  
 (torch.distributed over RCCL, one rank per GPU) every rank processes its own chunks (sites shard with no
 cross-site dependence) and the per-site probabilities are gathered over xGMI each step.
 
-Prints ONE JSON line (rank 0).  `roofline` is measured live with HIP events around the dominant kernel
-(the BiGRU layer-2 recurrent kernel), `cpu_baseline` times the CPU oracle on a bounded sample of the same
-workload on the host cores of this box.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the headline
+(`value`, `ms_per_step`, ...); `--dump-outputs DIR` writes the last timed step's per-site outputs as .npy files.
+Everything else is behind `--full`: `roofline` measured live with HIP events around the dominant kernel
+(the BiGRU layer-2 recurrent kernel), `cpu_baseline` timing the CPU oracle on a bounded sample of the same
+workload on the host cores of this box, the sustained run, the other configs and the file-to-file legs.
 """
 import argparse
 import json
@@ -79,7 +81,7 @@ def live_pmc_traffic(batch, timeout_s=240):
         for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
             out = os.path.join(tmp, ctr)
             cmd = [exe, "--kernel-trace", "--pmc", ctr, "--output-format", "csv", "-d", out, "--", sys.executable, os.path.join(ROOT, "bench.py"),
-                   "--steps", "3", "--warmup", "1", "--pool", "2", "--no-cpu-baseline", "--no-e2e", "--no-sustained", "--no-split", "--no-configs",
+                   "--full", "--steps", "3", "--warmup", "1", "--pool", "2", "--no-cpu-baseline", "--no-e2e", "--no-sustained", "--no-split", "--no-configs",
                    "--no-postfilters", "--no-live-traffic"]
             try:
                 r = subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True, text=True, timeout=timeout_s)
@@ -674,6 +676,21 @@ def hapfilter_many_calls(n_contigs=216, indel_every=4):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+def dump_outputs(dirname, out, gathered=None):
+    """The per-site outputs of one step, as a caller of Engine.run_device receives them, to dirname/<name>.npy (floating arrays
+    keep their dtype, integer ones become float64: exact); `gathered` = the all_gather buffer of that step when N > 1."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: out[k] for k in ("probs", "post", "decision", "qual", "aff_logits", "neg_logits", "site_info")}
+    if gathered is not None:
+        arrays["probs_all_ranks"] = gathered
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def self_launch(n):
     """Re-exec this command line under torch.distributed.run with n ranks on this node (rendezvous on 127.0.0.1, a free
     port); the ranks' stdout is ours, so rank 0's JSON line is the only line printed.  Returns the launcher's exit code."""
@@ -713,6 +730,11 @@ def main():
                     "device form; `hapfilter`: the long-read haplotype filter) - after the timed region, never part of `value`")
     ap.add_argument("--no-e2e", action="store_true", help="skip the file-to-file legs (mpileup text -> VCF, BAM -> VCF)")
     ap.add_argument("--e2e-chunks", type=int, default=96, help="chunk files of the mpileup-text leg (the BAM leg uses a third as many)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, run every side measurement and check as well (live roofline "
+                    "bracket in the timed region, gather census, sustained run, per-stage times, CPU baseline, split-operand, config, post-filter "
+                    "and file-to-file legs; the --no-* options above switch single legs off); off: the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's per-site outputs (probabilities, "
+                    "posterior, decision, QUAL, network logits, site info) to DIR/<name>.npy as float32 / float64")
     args = ap.parse_args()
 
     import numpy as np
@@ -821,17 +843,42 @@ def main():
     for i in range(args.warmup):
         step(i)
     sync()
-    check(lib.cto_model_profile(eng.h_neg, 1))
+    if args.full:
+        check(lib.cto_model_profile(eng.h_neg, 1))
     t0 = time.perf_counter()
     for i in range(args.steps):
         out = step(i)
     sync()
     dt = time.perf_counter() - t0
-    check(lib.cto_model_profile(eng.h_neg, 0))
+    if args.full:
+        check(lib.cto_model_profile(eng.h_neg, 0))
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, gather_buf[(args.steps - 1) & 1] if world > 1 else None)
+
+    sites_total = world * args.steps * args.batch
+    head = {
+        "metric": "candidate sites/sec (pileup-tensor + AFF/NEG inference) at 1/2/4/8 MI355X",
+        "value": round(sites_total / dt, 1), "unit": "sites/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "ONT 50x synthetic pileups, SNV (K=4), 1M-site job cut into %d-site chunks "
+                               "(BASELINE.json configs[1]); step = featurize(AFF+NEG) + CvT + BiGRU + posterior on one chunk"
+                               % args.batch,
+                   "batch": args.batch, "chunks_resident_per_gpu": args.pool, "min_bq_aff": min_bq,
+                   "pack_bytes_per_chunk": int(pack_bytes),
+                   "parallelism": "sites sharded, 1 rank/GPU" + (", all_gather of per-site probabilities (RCCL)" if world > 1 else ""),
+                   "weights": "seeded random init (no pretrained weights offline)"},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(head))
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # ---- proof that the exchange step ran between `world` distinct ranks: every rank's last per-site block must sit in its
     # rank-major slot of the gathered buffer, bit for bit, and every rank reports the device it computed on ----
@@ -968,19 +1015,8 @@ def main():
     if rank == 0 and world == 1 and not args.no_live_traffic:
         live_traffic = live_pmc_traffic(args.batch)
     if rank == 0:
-        sites_total = world * args.steps * args.batch
-        res = {
-            "metric": "candidate sites/sec (pileup-tensor + AFF/NEG inference) at 1/2/4/8 MI355X",
-            "value": round(sites_total / dt, 1), "unit": "sites/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "ONT 50x synthetic pileups, SNV (K=4), 1M-site job cut into %d-site chunks "
-                                   "(BASELINE.json configs[1]); step = featurize(AFF+NEG) + CvT + BiGRU + posterior on one chunk"
-                                   % args.batch,
-                       "batch": args.batch, "chunks_resident_per_gpu": args.pool, "min_bq_aff": min_bq,
-                       "pack_bytes_per_chunk": int(pack_bytes),
-                       "parallelism": "sites sharded, 1 rank/GPU" + (", all_gather of per-site probabilities (RCCL)" if world > 1 else ""),
-                       "weights": "seeded random init (no pretrained weights offline)"},
+        res = dict(head)
+        res.update({
             "roofline": {"bound": "mfma", "kernel": "k_gru_layer_rot<256,256,192,2,true> (BiGRU layer 2 + fused fc1, both directions)",
                          "achieved": round(achieved, 3), "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s",
                          "frac": round(achieved / PEAK_FP32_MFMA_TFLOPS, 4),
@@ -1008,7 +1044,7 @@ def main():
             "ranks_seen": dist.get_world_size() if world > 1 else 1,
             "backend": (dist.get_backend() + (" (RCCL over xGMI)" if backend == "nccl" else " (test hook)")) if world > 1 else None,
             "rank_devices": census, "gather_verified": gather_ok,
-        }
+        })
         if sustained is not None:
             res["sustained"] = sustained
         if stage_fracs is not None:

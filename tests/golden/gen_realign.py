@@ -23,7 +23,14 @@ consensus strings are an INPUT (recorded per window), everything else is the ref
   realign_flow.json.gz  {"seed", "inputs_sha256", "vcf": output VCF text, "vcf_indel": the same with --is_indel, "positions": {pos: {"sha256", "n_rows", "moved": [[name, pos,
                          cigar], ...]}}, "consensus": [[window reference, [haplotypes]], ...] in call order}
 
-Usage: make -C oracle ref && python tests/golden/gen_realign.py [windows|flow]     (from the repo root; build container only)
+`fresh` target: the windows of the tests that compare against the compiled reference on fresh windows, drawn from fixed seeds, with
+what the reference returned, so that those tests hold without oracle/_ref too -
+
+  realign_fresh.json.gz  {"host": {"seed", "inputs_sha256", "windows"}, "thousand": {...}, "device": {...}}  (windows as above; "host":
+                         120 windows, "thousand": one window of 1 000 reads from seed 7, "device": 400 windows + windows of 300 and
+                         1 000 reads, drawn in that order)
+
+Usage: make -C oracle ref && python tests/golden/gen_realign.py [windows|flow|fresh]     (from the repo root; build container only)
 """
 import gzip
 import hashlib
@@ -64,6 +71,34 @@ def main():
         with gzip.GzipFile(fileobj=f, mode="wb", mtime=0) as g:
             g.write(raw)
     print("wrote realign.json.gz: %d windows, %d reads, %d realigned, %d bytes raw" % (N_WINDOWS, reads, moved, len(raw)))
+
+
+FRESH = {"host": (20261016, [None] * 120), "thousand": (7, [1000]), "device": (20261017, [None] * 400 + [300, 1000])}
+
+
+def fresh_windows(which):
+    """the windows of one set of realign_fresh.json.gz, regenerated from its seed"""
+    seed, sizes = FRESH[which]
+    rng = np.random.default_rng(seed)
+    return [ru.gen_window(rng) if n is None else ru.gen_window(rng, n_reads=n) for n in sizes]
+
+
+def gen_fresh():
+    assert ru.ref_lib() is not None, "run `make -C oracle ref` first"
+    out = {}
+    for which in FRESH:
+        h = hashlib.sha256()
+        wins = []
+        for w in fresh_windows(which):
+            window_digest(h, w)
+            pos, cig = ru.ref_realign(w)
+            wins.append([[p - w["ref_start"], c] for p, c in zip(pos, cig)])
+        out[which] = {"seed": FRESH[which][0], "inputs_sha256": h.hexdigest(), "windows": wins}
+    raw = json.dumps(out, separators=(",", ":")).encode()
+    with open(os.path.join(HERE, "realign_fresh.json.gz"), "wb") as f:
+        with gzip.GzipFile(fileobj=f, mode="wb", mtime=0) as g:
+            g.write(raw)
+    print("wrote realign_fresh.json.gz: %s windows, %d bytes raw" % ({k: len(v["windows"]) for k, v in out.items()}, len(raw)))
 
 
 def flow_inputs_digest(paths):
@@ -159,3 +194,5 @@ if __name__ == "__main__":
         main()
     if which in ("all", "flow"):
         gen_flow()
+    if which in ("all", "fresh"):
+        gen_fresh()

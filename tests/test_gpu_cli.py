@@ -149,7 +149,7 @@ def test_bench_multi_rank_code_path(tmp_path, launcher):
     env = dict(os.environ, CTO_BENCH_BACKEND="gloo", CTO_BENCH_DEVICE="0", MASTER_ADDR="127.0.0.1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--pool", "2"]
+    tail = [os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--pool", "2"]
     if launcher == "torchrun":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                "127.0.0.1", "--master-port", "29533"] + tail
@@ -168,6 +168,44 @@ def test_bench_multi_rank_code_path(tmp_path, launcher):
     assert res["sustained"]["steps"] == 245 and res["sustained"]["sites"] == 2 * 245 * res["config"]["batch"] and res["sustained"]["sites_per_s"] > 0
 
 
+def test_bench_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """`bench.py --steps N --warmup W` without --full: one short JSON line with the headline fields only, `value` and `ms_per_step`
+    from the same N timed steps; --dump-outputs DIR holds the last timed step's outputs, equal to what the engine computes on that
+    step's chunk in this process."""
+    import json
+    import subprocess
+    import sys
+    import torch
+    from conftest import ROOT
+    from clairs_to_amd.engine import Engine, synthetic_models
+    from clairs_to_amd.synth import SynthChunk, likelihood_table, lik_and_edges
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "CTO_BENCH_BACKEND", "CTO_BENCH_DEVICE"):
+        env.pop(k, None)
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--pool", "2",
+                        "--dump-outputs", str(out)], env=env, cwd=ROOT, capture_output=True, text=True, timeout=280)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.split("\n") if l.startswith("{")]
+    assert len(lines) == 1 and len(lines[0]) < 4096
+    res = json.loads(lines[0])
+    assert res["n_gpus"] == 1 and res["steps"] == 3 and res["warmup"] == 1 and res["value"] > 0 and res["ms_per_step"] > 0
+    assert res["unit"] == "sites/s" and res["higher_is_better"] is True and res["dtype"] == "f32" and res["metric"]
+    assert abs(res["value"] * res["ms_per_step"] * 1e-3 / res["config"]["batch"] - 1.0) < 1e-3
+    assert "roofline" not in res and "cpu_baseline" not in res and "sustained" not in res and "e2e" not in res
+    # the last timed step (i = 2) ran resident chunk 2 % pool = 0 of rank 0
+    dev = torch.device("cuda:0")
+    chunk = SynthChunk(4096, seed=20260928, start=100000)
+    models = synthetic_models(4, seed=0)
+    lik, edges = lik_and_edges(likelihood_table(4), 4)
+    want = Engine(models["aff"], models["neg"], lik, edges, min_bq=20, device=dev).run_chunk(chunk.arrays(), chunk.site_pos)
+    torch.cuda.synchronize()
+    for name in ("probs", "post", "decision", "qual", "aff_logits", "neg_logits", "site_info"):
+        got = np.load(out / (name + ".npy"))
+        assert got.dtype in (np.float32, np.float64), name
+        assert np.array_equal(got, want[name].cpu().numpy().astype(got.dtype)), name
+
+
 def test_bench_eight_rank_dry_run(tmp_path):
     """The driver's first SCALE run must not die on set-up: `python bench.py --gpus 8` with its DEFAULT geometry (16 resident
     4096-site chunks per rank, the default steps and warm-up) as eight ranks on this box's single GPU over gloo (test hooks) - eight times the
@@ -182,7 +220,7 @@ def test_bench_eight_rank_dry_run(tmp_path):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     t0 = time.time()
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--watchdog", "560"], env=env, cwd=ROOT,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "8", "--watchdog", "560"], env=env, cwd=ROOT,
                        capture_output=True, text=True, timeout=600)
     took = time.time() - t0
     assert r.returncode == 0, r.stderr[-3000:]
@@ -211,7 +249,7 @@ def test_bench_two_ranks_over_rccl(tmp_path):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "CTO_BENCH_BACKEND", "CTO_BENCH_DEVICE"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--pool", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--pool", "2",
                         "--watchdog", "240"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stderr[-3000:]
     res = json.loads([l for l in r.stdout.split("\n") if l.startswith("{")][-1])

@@ -1,8 +1,8 @@
 """The device form of the Illumina realigner (csrc/realign_batch.hip; SURVEY.md 8f #4b, the `realign_reads` leg of BASELINE
 configs[3]): k_fast_pass (src/realign/realigner.cpp:129-229) and k_sw_ends (src/realign/ssw.c:118-529 as ssw_align drives them,
 :781-830) for every window of a batch, traceback and CIGAR composition on the host - POS and CIGAR of every read byte for byte
-what the reference's own realigner.cpp + SSW return (oracle/_ref/librealigner_ref.so, compiled from /root/reference by
-`make -C oracle ref`; it travels to the GPU box as a built file) and what the committed golden windows hold."""
+what the reference's own realigner.cpp + SSW return (oracle/_ref/librealigner_ref.so, compiled from the reference's sources by
+`make -C oracle ref`, where it is built) and what the committed golden windows hold."""
 import gzip
 import json
 import os
@@ -39,8 +39,16 @@ def test_device_realigner_on_the_golden_windows(dev):
         st["windows"], st["reads"], st["fast_pass_ms"], st["fast_pairs"], st["sw_ms"], st["sw_pairs"], st["sw_cells"]))
 
 
-@pytest.mark.skipif(ru.ref_lib() is None, reason="oracle/_ref/librealigner_ref.so not built (`make -C oracle ref`, needs /root/reference)")
 def test_device_realigner_equals_the_compiled_reference_on_fresh_windows(dev):
+    """402 windows of a fixed seed (up to 1 000 reads) against what the compiled reference returned on them (stored in
+    tests/golden/realign_fresh.json.gz); where oracle/_ref/ is built, windows of a fresh seed against the reference itself as well"""
+    from test_realign import fresh_set
+    ws, want = fresh_set("device")
+    got = ru.amd_realign_batch(ws, "device", threads=8)
+    bad = [i for i, (g, r) in enumerate(zip(got, want)) if g != r]
+    assert not bad, "stored windows %s differ from the reference's output" % bad[:10]
+    if ru.ref_lib() is None:
+        return
     seed = int.from_bytes(os.urandom(4), "little")
     rng = np.random.default_rng(seed)
     ws = [ru.gen_window(rng) for _ in range(400)] + [ru.gen_window(rng, n_reads=n) for n in (300, 1000)]

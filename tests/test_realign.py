@@ -1,9 +1,9 @@
 """Illumina realigner (SURVEY.md 8f #4b): cto_realign_reads against the reference's own native code.
 
 Pins: (1) tests/golden/realign.json.gz - what the reference's `realign_reads` (src/realign/realigner.cpp:782-869, compiled here by
-`make -C oracle ref`) returned on 640 synthetic windows, regenerated inputs checked by SHA-256; (2) when oracle/_ref/ is present,
-fresh windows against the compiled reference itself; (3) the reference-ABI shim libraries (clairs_to_amd/realign/*.so), called the
-way src/realign_reads.py:532-615 calls the reference's modules; (4) the striped Smith-Waterman pass alone (SSE2 in the product)
+`make -C oracle ref`) returned on 640 synthetic windows, regenerated inputs checked by SHA-256; (2) tests/golden/realign_fresh.json.gz -
+what it returned on windows of fixed seeds - and, when oracle/_ref/ is present, fresh windows against the compiled reference itself;
+(3) the reference-ABI shim libraries (clairs_to_amd/realign/*.so), called the way src/realign_reads.py:532-615 calls the reference's modules; (4) the striped Smith-Waterman pass alone (SSE2 in the product)
 against its scalar model in oracle/ssw_model.cpp.  The de Bruijn consensus has no compiled reference here (Boost):
 hand-derived vectors and properties only - PARITY UNPINNED."""
 import ctypes as C
@@ -13,7 +13,6 @@ import json
 import os
 
 import numpy as np
-import pytest
 
 import realignutil as ru
 
@@ -46,8 +45,29 @@ def test_realign_reads_equals_the_reference_on_the_golden_windows():
     assert len(g["windows"]) >= 500 and realigned > 10000 and fallback > 2000
 
 
-@pytest.mark.skipif(ru.ref_lib() is None, reason="oracle/_ref/librealigner_ref.so not built (`make -C oracle ref`, needs /root/reference)")
+def fresh_set(which):
+    """(windows, what the compiled reference returned on them) of one set of tests/golden/realign_fresh.json.gz
+    (gen_realign.py fresh), the windows regenerated from the stored seed and checked by SHA-256"""
+    import sys
+    sys.path.insert(0, os.path.join(HERE, "golden"))
+    from gen_realign import fresh_windows, window_digest
+    g = load("realign_fresh.json.gz")[which]
+    ws = fresh_windows(which)
+    h = hashlib.sha256()
+    for w in ws:
+        window_digest(h, w)
+    assert h.hexdigest() == g["inputs_sha256"], "the window generator changed: regenerate tests/golden/realign_fresh.json.gz"
+    return ws, [([p + w["ref_start"] for p, _ in want], [c for _, c in want]) for w, want in zip(ws, g["windows"])]
+
+
 def test_realign_reads_equals_the_compiled_reference_on_fresh_windows():
+    """120 windows of a fixed seed against what the compiled reference returned on them (stored); where oracle/_ref/ is built,
+    120 windows of a fresh seed against the compiled reference itself as well"""
+    ws, want = fresh_set("host")
+    for i, (w, r) in enumerate(zip(ws, want)):
+        assert ru.amd_realign(w) == r, "stored window %d" % i
+    if ru.ref_lib() is None:
+        return
     seed = int.from_bytes(os.urandom(4), "little")
     rng = np.random.default_rng(seed)
     for i in range(120):
@@ -55,12 +75,12 @@ def test_realign_reads_equals_the_compiled_reference_on_fresh_windows():
         assert ru.amd_realign(w) == ru.ref_realign(w), "window %d of np.random.default_rng(%d)" % (i, seed)
 
 
-@pytest.mark.skipif(ru.ref_lib() is None, reason="oracle/_ref/librealigner_ref.so not built")
 def test_realign_reads_full_window_of_a_thousand_reads():
     """max_region_reads_num = 1000 (src/realign_reads.py:51): the largest call the reference makes"""
-    rng = np.random.default_rng(7)
-    w = ru.gen_window(rng, n_reads=1000)
-    assert ru.amd_realign(w) == ru.ref_realign(w)
+    (w,), (want,) = fresh_set("thousand")
+    assert ru.amd_realign(w) == want
+    if ru.ref_lib() is not None:
+        assert want == ru.ref_realign(w)
 
 
 def _random_pair(rng, it):
