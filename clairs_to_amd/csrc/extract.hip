@@ -8,6 +8,7 @@
 #include <mutex>
 #include "common.h"
 #include "pack_internal.h"
+#include "scan.h"
 
 namespace {
 
@@ -232,24 +233,6 @@ __global__ __launch_bounds__(256) void k_cand_count(const uint8_t* __restrict__ 
     __syncthreads();
     if (threadIdx.x == 0) block_cnt[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
 }
-__global__ __launch_bounds__(1024) void k_cand_scan(int32_t* __restrict__ block_cnt, int n_blocks, int32_t* __restrict__ total) {   // one workgroup
-    __shared__ int part[1024];
-    const int t = threadIdx.x, per = (n_blocks + 1023) / 1024;
-    const int lo = min(n_blocks, t * per), hi = min(n_blocks, lo + per);
-    int s = 0;
-    for (int i = lo; i < hi; ++i) s += block_cnt[i];
-    part[t] = s;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const int v = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    int run = part[t] - s;
-    for (int i = lo; i < hi; ++i) { const int v = block_cnt[i]; block_cnt[i] = run; run += v; }       // exclusive
-    if (t == 1023) *total = part[t];
-}
 __global__ __launch_bounds__(256) void k_cand_scatter(const uint8_t* __restrict__ flags, const int32_t* __restrict__ col_pos, int64_t n, int bit,
                                                       int32_t lo, int32_t hi, const int32_t* __restrict__ block_base, int32_t* __restrict__ out,
                                                       int64_t cap) {
@@ -325,7 +308,7 @@ extern "C" int cto_candidate_positions(const cto_pack_view* dp, const uint8_t* f
     const int64_t nb = cto::cdiv(dp->n_cols, 256);
     CTO_REQUIRE(nb < (int64_t(1) << 30), CTO_EUNSUPPORTED, "cto_candidate_positions: too many columns");
     hipLaunchKernelGGL(k_cand_count, dim3(unsigned(nb)), dim3(256), 0, s, flags, dp->col_pos, dp->n_cols, bit, lo, hi, scratch);
-    hipLaunchKernelGGL(k_cand_scan, dim3(1), dim3(1024), 0, s, scratch, int(nb), n_out);
+    hipLaunchKernelGGL(k_scan_small<int32_t>, dim3(1), dim3(1024), 0, s, scratch, scratch, int(nb), n_out);     // in place: scratch[nb] = the sum
     hipLaunchKernelGGL(k_cand_scatter, dim3(unsigned(nb)), dim3(256), 0, s, flags, dp->col_pos, dp->n_cols, bit, lo, hi, scratch, out_pos, cap);
     CTO_HIP(hipGetLastError());
     return CTO_OK;

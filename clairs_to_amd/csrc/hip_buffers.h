@@ -1,0 +1,68 @@
+// Host-side plumbing of the device front end (pipeline.hip, pileup.hip, tokenise.hip): buffers that only grow, on the device and
+// page-locked on the host, and waits for the device that sleep instead of spinning.
+#pragma once
+#include <unistd.h>
+#include <cstring>
+#include "common.h"
+
+namespace cto {
+
+// what a buffer grows to when `n` bytes do not fit: room for a quarter more, so that slowly growing chunks reallocate rarely
+inline size_t grown_capacity(size_t n) { return n + n / 4 + 4096; }
+
+struct DevBuf {                          // a device allocation that only grows (its bytes do not survive growth)
+    void* p = nullptr;
+    size_t cap = 0;
+    int ensure(size_t n) {
+        if (n <= cap) return CTO_OK;
+        if (p) CTO_HIP(hipFree(p));
+        p = nullptr;
+        cap = 0;
+        const size_t want = grown_capacity(n);
+        CTO_HIP(hipMalloc(&p, want));
+        cap = want;
+        return CTO_OK;
+    }
+    template <class T> T* as() const { return static_cast<T*>(p); }
+    ~DevBuf() { if (p) (void)hipFree(p); }
+};
+
+struct PinBuf {                          // page-locked host memory that only grows
+    void* p = nullptr;
+    size_t cap = 0;
+    int ensure(size_t n) { return grow_keeping(n, 0); }
+    int grow_keeping(size_t n, size_t keep) {              // ensure(n) that carries the first `keep` bytes over
+        if (n <= cap) return CTO_OK;
+        void* q = nullptr;
+        const size_t want = grown_capacity(n);
+        CTO_HIP(hipHostMalloc(&q, want, hipHostMallocDefault));
+        if (p) {
+            if (keep) memcpy(q, p, keep);
+            CTO_HIP(hipHostFree(p));
+        }
+        p = q;
+        cap = want;
+        return CTO_OK;
+    }
+    template <class T> T* as() const { return static_cast<T*>(p); }
+    ~PinBuf() { if (p) (void)hipHostFree(p); }
+};
+
+// Waits for an event without occupying a core: hipEventSynchronize / hipStreamSynchronize poll the completion signal from the calling
+// thread (measured: every chunk waiting for the device inflate cost a second of CPU), and the producer and writer threads that wait
+// share the host with the threads that tokenise and inflate.
+inline hipError_t wait_event(hipEvent_t ev) {
+    for (int spins = 0;; ++spins) {
+        const hipError_t e = hipEventQuery(ev);
+        if (e != hipErrorNotReady) return e;
+        if (spins >= 4) usleep(spins < 64 ? 50 : 200);
+    }
+}
+
+// the same for everything queued on `s` so far
+inline hipError_t record_and_wait(hipEvent_t ev, hipStream_t s) {
+    const hipError_t e = hipEventRecord(ev, s);
+    return e != hipSuccess ? e : wait_event(ev);
+}
+
+}  // namespace cto

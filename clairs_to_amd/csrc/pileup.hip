@@ -30,14 +30,15 @@
 // order dependent), reference skips (N), --max-depth or more reads open at some read's start (the cap is order dependent; k_live_marks), a column
 // deeper than 2048, 2048 or more reads open at a read's start, or more than 64 distinct indel keys in a column.  The BGZF CRC-32 of every block is
 // checked on the device (k_crc32_blocks), as htslib and the host reader check it.
-#include <unistd.h>
 #include <algorithm>
 #include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
 #include "common.h"
+#include "hip_buffers.h"
 #include "pack_internal.h"
+#include "scan.h"
 
 using namespace cto;
 
@@ -138,93 +139,6 @@ __global__ void k_chain(const uint8_t* __restrict__ lin, int64_t len, const int6
     }
     if (o > limit) atomicExch(&fl->bad_chain, 1);              // a named offset that is not a record boundary
     if (!mode) counts[k] = n;
-}
-
-// Exclusive prefix sum across the 1024 threads of the one workgroup these scan kernels run as (wave shuffles, then the 16 wave
-// totals through LDS); *total = the sum.  Two barriers.
-__device__ __forceinline__ long long block_scan_excl(long long v, long long* total, long long* wsum /* [17] shared */) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const long long u = __shfl_up(inc, d);
-        if (lane >= d) inc += u;
-    }
-    __syncthreads();                                          // wsum may still be read from the previous call
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    long long before = 0, all = 0;
-    for (int w = 0; w < 16; ++w) { const long long x = wsum[w]; if (w < wave) before += x; all += x; }
-    *total = all;
-    return before + inc - v;
-}
-
-// exclusive prefix sums of an int array by one workgroup of 1024 threads, 4096 elements per pass (coalesced)
-template <typename Out>
-__global__ __launch_bounds__(1024) void k_scan_small(const int* __restrict__ in, Out* __restrict__ out, int n, Out* total) {
-    __shared__ long long wsum[17];
-    const int t = threadIdx.x;
-    long long carry = 0;
-    for (int base = 0; base < n; base += 4096) {
-        const int i0 = base + 4 * t;
-        int v[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = i0 + k < n ? in[i0 + k] : 0;
-        long long tot;
-        long long ex = carry + block_scan_excl((long long)v[0] + v[1] + v[2] + v[3], &tot, wsum);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { if (i0 + k < n) out[i0 + k] = Out(ex); ex += v[k]; }
-        carry += tot;
-    }
-    if (t == 0) { out[n] = Out(carry); if (total) *total = Out(carry); }
-}
-
-// The same over arrays of any length, spread over the chip: block sums of 4096-element tiles, their scan by one workgroup, then
-// every tile scans itself on top of its base (a region piled up at every position has a million columns: the one-workgroup
-// form above took 0.7 ms for them, the three launches below ~15 us).
-constexpr int SCAN_TILE = 4096;
-__global__ __launch_bounds__(1024) void k_tile_sums(const int* __restrict__ in, int n, long long* __restrict__ tsum) {
-    __shared__ long long wsum[17];
-    const int i0 = blockIdx.x * SCAN_TILE + 4 * threadIdx.x;
-    long long v = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v += i0 + k < n ? in[i0 + k] : 0;
-    long long tot;
-    (void)block_scan_excl(v, &tot, wsum);
-    if (threadIdx.x == 0) tsum[blockIdx.x] = tot;
-}
-// exclusive scan in place of up to three interleaved arrays of tile sums (a[i * stride + j], j < stride) by one workgroup;
-// totals[j] receives the sums
-__global__ __launch_bounds__(1024) void k_scan_tiles(long long* __restrict__ a, int n, int stride, long long* __restrict__ totals) {
-    __shared__ long long wsum[17];
-    const int t = threadIdx.x;
-    for (int j = 0; j < stride; ++j) {
-        long long carry = 0;
-        for (int base = 0; base < n; base += 1024) {
-            const int i = base + t;
-            const long long v = i < n ? a[size_t(i) * stride + j] : 0;
-            long long tot;
-            const long long ex = carry + block_scan_excl(v, &tot, wsum);
-            if (i < n) a[size_t(i) * stride + j] = ex;
-            carry += tot;
-        }
-        if (t == 0) totals[j] = carry;
-        __syncthreads();
-    }
-}
-template <typename Out>
-__global__ __launch_bounds__(1024) void k_scan_apply(const int* __restrict__ in, Out* __restrict__ out, int n, const long long* __restrict__ tbase,
-                                                     const long long* __restrict__ totals, Out* total) {
-    __shared__ long long wsum[17];
-    const int i0 = blockIdx.x * SCAN_TILE + 4 * threadIdx.x;
-    int v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = i0 + k < n ? in[i0 + k] : 0;
-    long long tot;
-    long long ex = tbase[blockIdx.x] + block_scan_excl((long long)v[0] + v[1] + v[2] + v[3], &tot, wsum);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { if (i0 + k < n) out[i0 + k] = Out(ex); ex += v[k]; }
-    if (blockIdx.x == 0 && threadIdx.x == 0) { out[n] = Out(totals[0]); if (total) *total = Out(totals[0]); }
 }
 
 __global__ void k_parse(const uint8_t* __restrict__ lin, const uint32_t* __restrict__ rec_off, int n_rec, int tid, int beg0, int end0,
@@ -784,73 +698,31 @@ __global__ void k_keys_str(int n_keys, const KeyRec* __restrict__ key_final, con
     }
 }
 
-struct Buf {
-    void* p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t n) {
-        if (n <= cap) return CTO_OK;
-        if (p) { CTO_HIP(hipFree(p)); p = nullptr; cap = 0; }
-        const size_t want = n + n / 4 + 4096;
-        CTO_HIP(hipMalloc(&p, want));
-        cap = want;
-        return CTO_OK;
-    }
-    ~Buf() { if (p) (void)hipFree(p); }
-    template <class T> T* as() { return static_cast<T*>(p); }
-};
-
 }  // namespace
 
 struct cto_dev_pileup {
-    Buf tile_a, tile_b, tile_tot;        // tile sums of the spread-out scans
-    Buf lin, counts, base, rec_off, reads, rid, live, diff, slot_col, col_slot, col_off, col_pos, col_ref, cursor, tmp,
+    DevBuf tile_a, tile_b, tile_tot;     // tile sums of the spread-out scans
+    DevBuf lin, counts, base, rec_off, reads, rid, live, diff, slot_col, col_slot, col_off, col_pos, col_ref, cursor, tmp,
         entries, nkc, keyrec, key_off, key_meta, key_group, key_final, key_col, key_len, str_off, key_str, z1k;
     bool z1k_ready = false;
-    Flags* h_flags = nullptr;            // page-locked mirror
-    void* h_stage = nullptr;             // page-locked landing area of the small arrays that go back to the host (a copy to pageable
-    size_t h_stage_cap = 0;              // memory blocks - and spins - until everything queued in front of it is done)
+    PinBuf h_flags;                      // page-locked mirror of the flags
+    PinBuf h_stage;                      // page-locked landing area of the small arrays that go back to the host (a copy to pageable
+                                         // memory blocks - and spins - until everything queued in front of it is done)
     // The chunk's small inputs (flags, block table, linear offsets, record starts, intervals, reference window) go up as ONE copy out
     // of page-locked memory: six hipMemcpyAsync calls from pageable vectors each pin their source on the fly, under a lock every
     // producer thread of the run shares.
-    Buf up;
-    void* h_up = nullptr;
-    size_t h_up_cap = 0;
-    int up_ensure(size_t n) {
-        if (n <= h_up_cap) return CTO_OK;
-        if (h_up) { CTO_HIP(hipHostFree(h_up)); h_up = nullptr; h_up_cap = 0; }
-        const size_t want = n + n / 4 + 4096;
-        CTO_HIP(hipHostMalloc(&h_up, want, hipHostMallocDefault));
-        h_up_cap = want;
-        return CTO_OK;
-    }
-    int stage_ensure(size_t n) {
-        if (n <= h_stage_cap) return CTO_OK;
-        if (h_stage) { CTO_HIP(hipHostFree(h_stage)); h_stage = nullptr; h_stage_cap = 0; }
-        const size_t want = n + n / 4 + 4096;
-        CTO_HIP(hipHostMalloc(&h_stage, want, hipHostMallocDefault));
-        h_stage_cap = want;
-        return CTO_OK;
-    }
-    hipEvent_t ev = nullptr;             // the driver's waits sleep on it: hipStreamSynchronize polls the completion signal from the calling
-                                         // thread, and that thread shares sixteen host cores with everything else of a run
-    ~cto_dev_pileup() { if (h_flags) (void)hipHostFree(h_flags); if (h_stage) (void)hipHostFree(h_stage); if (h_up) (void)hipHostFree(h_up); if (ev) (void)hipEventDestroy(ev); }
+    DevBuf up;
+    PinBuf h_up;
+    hipEvent_t ev = nullptr;             // the driver's waits sleep on it (record_and_wait): hipStreamSynchronize polls the completion signal
+                                         // from the calling thread, and that thread shares sixteen host cores with everything else of a run
+    ~cto_dev_pileup() { if (ev) (void)hipEventDestroy(ev); }
 };
-
-// waits for everything queued on `s` so far without occupying a core (pipeline.hip's wait_event)
-static hipError_t sleepy_sync(cto_dev_pileup* cx, hipStream_t s) {
-    hipError_t e = hipEventRecord(cx->ev, s);
-    if (e != hipSuccess) return e;
-    for (int spins = 0;; ++spins) {
-        e = hipEventQuery(cx->ev);
-        if (e != hipErrorNotReady) return e;
-        if (spins >= 4) usleep(spins < 64 ? 50 : 200);
-    }
-}
 
 extern "C" int cto_dev_pileup_create(cto_dev_pileup** out) try {
     CTO_REQUIRE(out, CTO_EINVAL, "cto_dev_pileup_create: null argument");
     std::unique_ptr<cto_dev_pileup> c(new cto_dev_pileup());
-    CTO_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_flags), sizeof(Flags), hipHostMallocDefault));
+    int rc;
+    if ((rc = c->h_flags.ensure(sizeof(Flags)))) return rc;
     CTO_HIP(hipEventCreateWithFlags(&c->ev, hipEventDisableTiming));
     *out = c.release();
     return CTO_OK;
@@ -908,11 +780,17 @@ extern "C" int cto_pileup_device(cto_dev_pileup* cx, const void* d_inflated, con
         ivs.push_back(int(total));
     }
     const int n_iv = int((ivs.size() - 1) / 3), total = ivs.back();
-    Flags* hf = cx->h_flags;
+    Flags* hf = cx->h_flags.as<Flags>();
     Flags* fl = nullptr;                 // the flags on the device (first part of the upload block, set below)
+    auto scan = [&](const int* in, int n, auto* out, auto* sum) -> int {        // scan.h's exclusive scan, its tile scratch grown to fit
+        int rc0;
+        if ((rc0 = cx->tile_a.ensure(size_t(cdiv(n, SCAN_TILE) + 1) * 8)) || (rc0 = cx->tile_tot.ensure(64))) return rc0;
+        scan_exclusive(s, in, n, out, sum, cx->tile_a.as<long long>(), cx->tile_tot.as<long long>());
+        return CTO_OK;
+    };
     auto fetch_flags = [&]() -> int {
         CTO_HIP(hipMemcpyAsync(hf, fl, sizeof(Flags), hipMemcpyDeviceToHost, s));
-        CTO_HIP(sleepy_sync(cx, s));
+        CTO_HIP(record_and_wait(cx->ev, s));
         return CTO_OK;
     };
     auto empty_result = [&]() -> int {
@@ -928,7 +806,7 @@ extern "C" int cto_pileup_device(cto_dev_pileup* cx, const void* d_inflated, con
             return rc0;
         CTO_HIP(hipMemsetAsync(cx->col_off.p, 0, 64, s));
         CTO_HIP(hipMemsetAsync(cx->key_off.p, 0, 64, s));
-        CTO_HIP(sleepy_sync(cx, s));
+        CTO_HIP(record_and_wait(cx->ev, s));
         dev_view->col_pos = cx->col_pos.as<int32_t>();
         dev_view->col_ref = cx->col_ref.as<uint8_t>();
         dev_view->col_off = cx->col_off.as<int64_t>();
@@ -953,9 +831,9 @@ extern "C" int cto_pileup_device(cto_dev_pileup* cx, const void* d_inflated, con
     const size_t up_bytes[6] = {sizeof(Flags), lin_off.size() * 8, size_t(n_blocks) * sizeof(cto_bgzf_block), starts.size() * 8, ivs.size() * 4, ref_len};
     size_t up_off[6], up_total = 0;
     for (int i = 0; i < 6; ++i) { up_off[i] = up_total; up_total += (up_bytes[i] + 255) / 256 * 256 + 256; }
-    if ((rc = cx->up.ensure(up_total)) || (rc = cx->up_ensure(up_total))) return rc;
-    for (int i = 0; i < 6; ++i) memcpy(static_cast<char*>(cx->h_up) + up_off[i], up_src[i], up_bytes[i]);
-    CTO_HIP(hipMemcpyAsync(cx->up.p, cx->h_up, up_total, hipMemcpyHostToDevice, s));
+    if ((rc = cx->up.ensure(up_total)) || (rc = cx->h_up.ensure(up_total))) return rc;
+    for (int i = 0; i < 6; ++i) memcpy(cx->h_up.as<char>() + up_off[i], up_src[i], up_bytes[i]);
+    CTO_HIP(hipMemcpyAsync(cx->up.p, cx->h_up.p, up_total, hipMemcpyHostToDevice, s));
     char* const d_up = static_cast<char*>(cx->up.p);
     fl = reinterpret_cast<Flags*>(d_up + up_off[0]);
     const int64_t* d_lin_off = reinterpret_cast<const int64_t*>(d_up + up_off[1]);
@@ -979,7 +857,7 @@ extern "C" int cto_pileup_device(cto_dev_pileup* cx, const void* d_inflated, con
     // ---- record boundaries ----
     const unsigned cgrid = unsigned(cdiv(n_chains, 64));
     hipLaunchKernelGGL(k_chain, dim3(cgrid), dim3(64), 0, s, lin, len, d_starts, n_chains, 0, cx->counts.as<int>(), nullptr, nullptr, fl);
-    hipLaunchKernelGGL(k_scan_small<int>, dim3(1), dim3(1024), 0, s, cx->counts.as<int>(), cx->base.as<int>(), n_chains, &fl->n_rec);
+    if ((rc = scan(cx->counts.as<int>(), n_chains, cx->base.as<int>(), &fl->n_rec))) return rc;
     CTO_HIP(hipGetLastError());
     if ((rc = fetch_flags())) return rc;
     if (hf->bad_crc) {
@@ -1047,16 +925,7 @@ extern "C" int cto_pileup_device(cto_dev_pileup* cx, const void* d_inflated, con
     hipLaunchKernelGGL(k_order, dim3(unsigned(std::min<long long>(cdiv(n_cols, 64), 65536))), dim3(64), 0, s, lin, cx->reads.as<DevRead>(), cx->rid.as<int>(),
                        n_cols, cx->col_off.as<long long>(), cx->cursor.as<int>(), cx->tmp.as<TmpEnt>(), cx->entries.as<uint32_t>(), cx->nkc.as<int>(),
                        cx->keyrec.as<KeyRec>(), max_indel_length, fl);
-    if (n_cols <= 4 * SCAN_TILE) {
-        hipLaunchKernelGGL(k_scan_small<int>, dim3(1), dim3(1024), 0, s, cx->nkc.as<int>(), cx->key_off.as<int>(), n_cols, &fl->n_keys);
-    } else {
-        const int tiles = int(cdiv(n_cols, SCAN_TILE));
-        if ((rc = cx->tile_a.ensure(size_t(tiles + 1) * 8)) || (rc = cx->tile_tot.ensure(64))) return rc;
-        hipLaunchKernelGGL(k_tile_sums, dim3(unsigned(tiles)), dim3(1024), 0, s, cx->nkc.as<int>(), n_cols, cx->tile_a.as<long long>());
-        hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(1024), 0, s, cx->tile_a.as<long long>(), tiles, 1, cx->tile_tot.as<long long>());
-        hipLaunchKernelGGL(k_scan_apply<int>, dim3(unsigned(tiles)), dim3(1024), 0, s, cx->nkc.as<int>(), cx->key_off.as<int>(), n_cols,
-                           cx->tile_a.as<long long>(), cx->tile_tot.as<long long>(), &fl->n_keys);
-    }
+    if ((rc = scan(cx->nkc.as<int>(), n_cols, cx->key_off.as<int>(), &fl->n_keys))) return rc;
     CTO_HIP(hipGetLastError());
     if ((rc = fetch_flags())) return rc;
     if (hf->ref_oob) { set_error("cto_pileup_device: a covered position lies outside the supplied reference"); return CTO_EINVAL; }
@@ -1076,7 +945,7 @@ extern "C" int cto_pileup_device(cto_dev_pileup* cx, const void* d_inflated, con
         hipLaunchKernelGGL(k_keys_meta, dim3(unsigned(cdiv(n_cols, 256))), dim3(256), 0, s, n_cols, cx->col_off.as<long long>(), cx->key_off.as<int>(),
                            cx->keyrec.as<KeyRec>(), cx->col_pos.as<int32_t>(), (long long)ref_start, (long long)ref_len, max_indel_length,
                            cx->key_meta.as<uint8_t>(), cx->key_group.as<int32_t>(), cx->key_final.as<KeyRec>(), cx->key_col.as<int>(), cx->key_len.as<int>());
-        hipLaunchKernelGGL(k_scan_small<long long>, dim3(1), dim3(1024), 0, s, cx->key_len.as<int>(), cx->str_off.as<long long>(), n_keys, &fl->key_str_bytes);
+        if ((rc = scan(cx->key_len.as<int>(), n_keys, cx->str_off.as<long long>(), &fl->key_str_bytes))) return rc;
         CTO_HIP(hipGetLastError());
         if ((rc = fetch_flags())) return rc;
         const long long sb = hf->key_str_bytes;
@@ -1099,11 +968,11 @@ extern "C" int cto_pileup_device(cto_dev_pileup* cx, const void* d_inflated, con
                         lite->col_ref.data(), lite->key_off.data()};
         size_t off[7], total = 0;
         for (int i = 0; i < 7; ++i) { off[i] = total; total += (bytes[i] + 63) / 64 * 64; }
-        if ((rc = cx->stage_ensure(total + 64))) return rc;
-        char* hs = static_cast<char*>(cx->h_stage);
+        if ((rc = cx->h_stage.ensure(total + 64))) return rc;
+        char* hs = cx->h_stage.as<char>();
         for (int i = 0; i < 7; ++i)
             if (bytes[i]) CTO_HIP(hipMemcpyAsync(hs + off[i], src[i], bytes[i], hipMemcpyDeviceToHost, s));
-        CTO_HIP(sleepy_sync(cx, s));
+        CTO_HIP(record_and_wait(cx->ev, s));
         for (int i = 0; i < 7; ++i)
             if (bytes[i]) memcpy(dst[i], hs + off[i], bytes[i]);
     }

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "common.h"
+#include "hip_buffers.h"
 #include "pack_internal.h"
 
 using namespace cto;
@@ -43,63 +44,8 @@ extern char** environ;
 
 namespace {
 
-// Waits for an event without occupying a core: hipEventSynchronize / hipStreamSynchronize poll the completion signal from the calling
-// thread (measured: every chunk waiting for the device inflate cost a second of CPU), and the producer and writer threads that wait
-// here share the host with the threads that tokenise and inflate.
-hipError_t wait_event(hipEvent_t ev) {
-    for (int spins = 0;; ++spins) {
-        const hipError_t e = hipEventQuery(ev);
-        if (e != hipErrorNotReady) return e;
-        if (spins >= 4) usleep(spins < 64 ? 50 : 200);
-    }
-}
-
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 double cpu_s() { timespec ts; clock_gettime(CLOCK_THREAD_CPUTIME_ID, &ts); return double(ts.tv_sec) + double(ts.tv_nsec) * 1e-9; }   // this thread's CPU time
-
-struct DevBuf {                          // a device allocation that only grows
-    void* p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t n) {
-        if (n <= cap) return CTO_OK;
-        if (p) CTO_HIP(hipFree(p));
-        p = nullptr;
-        cap = 0;
-        const size_t want = n + n / 4 + 256;
-        CTO_HIP(hipMalloc(&p, want));
-        cap = want;
-        return CTO_OK;
-    }
-    ~DevBuf() { if (p) (void)hipFree(p); }
-};
-struct PinBuf {                          // page-locked host memory that only grows
-    void* p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t n) {
-        if (n <= cap) return CTO_OK;
-        if (p) CTO_HIP(hipHostFree(p));
-        p = nullptr;
-        cap = 0;
-        const size_t want = n + n / 4 + 256;
-        CTO_HIP(hipHostMalloc(&p, want, hipHostMallocDefault));
-        cap = want;
-        return CTO_OK;
-    }
-    int grow_keeping(size_t n, size_t keep) {              // ensure(n) that carries the first `keep` bytes over
-        if (n <= cap) return CTO_OK;
-        void* q = nullptr;
-        const size_t want = n + n / 4 + 256;
-        CTO_HIP(hipHostMalloc(&q, want, hipHostMallocDefault));
-        if (p) {
-            if (keep) memcpy(q, p, keep);
-            CTO_HIP(hipHostFree(p));
-        }
-        p = q;
-        cap = want;
-        return CTO_OK;
-    }
-    ~PinBuf() { if (p) (void)hipHostFree(p); }
-};
 
 struct Slot {
     // pack on the device

@@ -20,13 +20,13 @@
 // the caller runs cto_pack_from_mpileup, which defines the behaviour (and words the errors).  Held bit-equal to it, array for array and
 // key string for key string, by tests/test_gpu_tokenise.py.
 #include <stdlib.h>
-#include <unistd.h>
 #include <algorithm>
 #include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
 #include "common.h"
+#include "hip_buffers.h"
 #include "pack_internal.h"
 
 using namespace cto;
@@ -43,127 +43,58 @@ struct TokFlags {
     long long n_entries, key_str_bytes;
 };
 
-struct Buf {
-    void* p = nullptr;
-    size_t cap = 0;
-    ~Buf() { if (p) (void)hipFree(p); }
-    int ensure(size_t n) {
-        if (n <= cap) return CTO_OK;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        const size_t want = n + n / 4 + 4096;
-        CTO_HIP(hipMalloc(&p, want));
-        cap = want;
-        return CTO_OK;
-    }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-
-// ---- exclusive scans (int32 in, T out) over up to 2^30 elements: tile sums, one workgroup over the tile sums, apply ----
+// Exclusive scan of the row counts of the 256-byte segments (a chunk's ~86 000) in ONE launch: a workgroup per SCAN_TILE elements adds
+// up the elements in front of its tile, then scans its own; out has n + 1 elements, out[n] = *total = the sum
 constexpr int SCAN_TILE = 4096;
-template <class T>
-__global__ __launch_bounds__(256) void k_tile_sum(const int* __restrict__ in, int n, T* __restrict__ tile_sum) {
-    __shared__ T part[256];
-    const int t0 = blockIdx.x * SCAN_TILE;
-    T s = 0;
-    for (int i = threadIdx.x; i < SCAN_TILE; i += 256) if (t0 + i < n) s += T(in[t0 + i]);
-    part[threadIdx.x] = s;
+__global__ __launch_bounds__(256) void k_seg_scan(const int* __restrict__ in, int n, int* __restrict__ out, int* __restrict__ total) {
+    __shared__ int part[256];
+    __shared__ int s_base;
+    // the elements in front of the tile, not tile sums (the last of 21 workgroups reads 340 KB out of the L2; tile sums by atomics from
+    // the counting kernel cost it 0.8 ms - 5 400 atomics on 21 addresses)
+    int b = 0;
+    {
+        // 16-byte loads, eight in flight per thread (one element per trip waited out an L2 round trip per element: 45 us)
+        const int4* in4 = reinterpret_cast<const int4*>(in);
+        const int n4 = int(blockIdx.x) * (SCAN_TILE / 4);
+        int i = threadIdx.x;
+        for (; i + 7 * 256 < n4; i += 8 * 256) {
+            int4 v[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = in4[i + k * 256];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) b += v[k].x + v[k].y + v[k].z + v[k].w;
+        }
+        for (; i < n4; i += 256) { const int4 v = in4[i]; b += v.x + v.y + v.z + v.w; }
+    }
+    part[threadIdx.x] = b;
     __syncthreads();
     for (int d = 128; d > 0; d >>= 1) { if (int(threadIdx.x) < d) part[threadIdx.x] += part[threadIdx.x + d]; __syncthreads(); }
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = part[0];
-}
-template <class T>
-__global__ __launch_bounds__(1024) void k_tile_scan(T* __restrict__ tile_sum, int n_tiles, T* __restrict__ total) {
-    __shared__ T part[1024];
-    T carry = 0;
-    for (int base = 0; base < n_tiles; base += 1024) {
-        const int i = base + threadIdx.x;
-        const T v = i < n_tiles ? tile_sum[i] : T(0);
-        part[threadIdx.x] = v;
-        __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {
-            const T a = int(threadIdx.x) >= d ? part[threadIdx.x - d] : T(0);
-            __syncthreads();
-            part[threadIdx.x] += a;
-            __syncthreads();
-        }
-        if (i < n_tiles) tile_sum[i] = carry + part[threadIdx.x] - v;
-        const T all = part[1023];
-        __syncthreads();
-        carry += all;
-    }
-    if (threadIdx.x == 0) *total = carry;
-}
-// SUMS: tile_base holds the tiles' SUMS (k_tile_sum's output, no k_tile_scan in between) and every workgroup adds up those in front of
-// its own - for the few dozen tiles of a chunk's rows and keys that is cheaper than a launch; `total` is then written here
-template <class T, bool SUMS>
-__global__ __launch_bounds__(256) void k_tile_apply(const int* __restrict__ in, int n, const T* __restrict__ tile_base, T* __restrict__ out,
-                                                    T* __restrict__ total) {
-    __shared__ T part[256];
-    __shared__ T s_base;
-    if (SUMS) {
-        // tile_base == nullptr: no tile sums at all - the workgroup adds up the ELEMENTS in front of its tile (a chunk's 86 000 segment counts:
-        // the last of 21 workgroups reads 340 KB out of the L2; tile sums by atomics from the counting kernel cost it 0.8 ms - 5 400 atomics
-        // on 21 addresses)
-        T b = 0;
-        if (tile_base == nullptr) {
-            // 16-byte loads, eight in flight per thread (one element per trip waited out an L2 round trip per element: 45 us)
-            const int4* in4 = reinterpret_cast<const int4*>(in);
-            const int n4 = int(blockIdx.x) * (SCAN_TILE / 4);
-            int i = threadIdx.x;
-            for (; i + 7 * 256 < n4; i += 8 * 256) {
-                int4 v[8];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) v[k] = in4[i + k * 256];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) b += T(v[k].x) + T(v[k].y) + T(v[k].z) + T(v[k].w);
-            }
-            for (; i < n4; i += 256) { const int4 v = in4[i]; b += T(v.x) + T(v.y) + T(v.z) + T(v.w); }
-        }
-        else for (int i = threadIdx.x; i < int(blockIdx.x); i += 256) b += tile_base[i];
-        part[threadIdx.x] = b;
-        __syncthreads();
-        for (int d = 128; d > 0; d >>= 1) { if (int(threadIdx.x) < d) part[threadIdx.x] += part[threadIdx.x + d]; __syncthreads(); }
-        if (threadIdx.x == 0) s_base = part[0];
-        __syncthreads();
-    }
-    const T tile0 = SUMS ? s_base : tile_base[blockIdx.x];
+    if (threadIdx.x == 0) s_base = part[0];
+    __syncthreads();
+    const int tile0 = s_base;
     __syncthreads();
     const int t0 = blockIdx.x * SCAN_TILE;
     constexpr int PER = SCAN_TILE / 256;
     const int i0 = t0 + threadIdx.x * PER;
-    T loc[PER];
-    T s = 0;
+    int loc[PER];
+    int s = 0;
 #pragma unroll
-    for (int k = 0; k < PER; ++k) { loc[k] = s; s += (i0 + k < n) ? T(in[i0 + k]) : T(0); }
+    for (int k = 0; k < PER; ++k) { loc[k] = s; s += (i0 + k < n) ? in[i0 + k] : 0; }
     part[threadIdx.x] = s;
     __syncthreads();
     for (int d = 1; d < 256; d <<= 1) {
-        const T a = int(threadIdx.x) >= d ? part[threadIdx.x - d] : T(0);
+        const int a = int(threadIdx.x) >= d ? part[threadIdx.x - d] : 0;
         __syncthreads();
         part[threadIdx.x] += a;
         __syncthreads();
     }
-    const T base = tile0 + part[threadIdx.x] - s;
+    const int base = tile0 + part[threadIdx.x] - s;
 #pragma unroll
     for (int k = 0; k < PER; ++k) if (i0 + k < n) out[i0 + k] = base + loc[k];
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 255) {
-        out[n] = tile0 + part[255];      // out has n + 1 elements
-        if (SUMS) *total = tile0 + part[255];
+        out[n] = tile0 + part[255];
+        *total = tile0 + part[255];
     }
-}
-template <class T>
-int scan_exclusive(hipStream_t s, const int* in, int n, T* out /* n + 1 */, T* tile_tmp, T* total) {
-    if (n <= 0) { CTO_HIP(hipMemsetAsync(out, 0, sizeof(T), s)); CTO_HIP(hipMemsetAsync(total, 0, sizeof(T), s)); return CTO_OK; }
-    const int tiles = int(cdiv(n, SCAN_TILE));
-    hipLaunchKernelGGL(k_tile_sum<T>, dim3(unsigned(tiles)), dim3(256), 0, s, in, n, tile_tmp);
-    if (tiles <= 256) {                 // a chunk's rows / keys: two launches instead of three
-        hipLaunchKernelGGL((k_tile_apply<T, true>), dim3(unsigned(tiles)), dim3(256), 0, s, in, n, tile_tmp, out, total);
-    } else {
-        hipLaunchKernelGGL(k_tile_scan<T>, dim3(1), dim3(1024), 0, s, tile_tmp, tiles, total);
-        hipLaunchKernelGGL((k_tile_apply<T, false>), dim3(unsigned(tiles)), dim3(256), 0, s, in, n, tile_tmp, out, total);
-    }
-    CTO_HIP(hipGetLastError());
-    return CTO_OK;
 }
 
 // ---- character classes of pack.cpp: 0..11 read-base code, 12 indel sign, 13 '^', 14 skipped, 15 ends a field (byte <= 10) ----
@@ -692,33 +623,12 @@ __global__ __launch_bounds__(64) void k_row_keys(RowArgs a) {
 }  // namespace
 
 struct cto_dev_tokeniser {
-    Buf text, ref, seg_cnt, seg_base, row_start, row_nt, row_nk, row_pos, row_b0, row_blen, row_tok, row_str, row_str_off, col_off, key_off, entries, col_pos, col_ref,
-        key_meta, key_group, str_off, key_str, tiles, row_tiles, codes, tok, flags;
-    void* h_text = nullptr; size_t h_text_cap = 0;      // page-locked: the text on its way up
-    void* h_stage = nullptr; size_t h_stage_cap = 0;    // page-locked: everything that comes back
-    hipEvent_t ev = nullptr;
-    ~cto_dev_tokeniser() {
-        if (h_text) (void)hipHostFree(h_text);
-        if (h_stage) (void)hipHostFree(h_stage);
-        if (ev) (void)hipEventDestroy(ev);
-    }
-    int pin(void** p, size_t* cap, size_t n) {
-        if (n <= *cap) return CTO_OK;
-        if (*p) { (void)hipHostFree(*p); *p = nullptr; *cap = 0; }
-        const size_t want = n + n / 4 + 65536;
-        CTO_HIP(hipHostMalloc(p, want, hipHostMallocDefault));
-        *cap = want;
-        return CTO_OK;
-    }
-    int wait(hipStream_t s) {          // a sleeping wait: hipStreamSynchronize spins, and the producer threads share the cores
-        CTO_HIP(hipEventRecord(ev, s));
-        for (;;) {
-            const hipError_t e = hipEventQuery(ev);
-            if (e == hipSuccess) return CTO_OK;
-            if (e != hipErrorNotReady) { set_error("cto_tokenise_device: %s", hipGetErrorString(e)); return CTO_EHIP; }
-            usleep(50);
-        }
-    }
+    DevBuf text, ref, seg_cnt, seg_base, row_start, row_nt, row_nk, row_pos, row_b0, row_blen, row_tok, row_str, row_str_off, col_off, key_off, entries,
+        col_pos, col_ref, key_meta, key_group, str_off, key_str, row_tiles, codes, tok, flags;
+    PinBuf h_text;                       // page-locked: the text on its way up
+    PinBuf h_stage;                      // page-locked: everything that comes back
+    hipEvent_t ev = nullptr;             // the waits sleep on it (record_and_wait): hipStreamSynchronize spins, and the producer threads share the cores
+    ~cto_dev_tokeniser() { if (ev) (void)hipEventDestroy(ev); }
 };
 
 extern "C" int cto_dev_tokeniser_create(cto_dev_tokeniser** out) try {
@@ -734,8 +644,8 @@ extern "C" void cto_dev_tokeniser_destroy(cto_dev_tokeniser* c) { delete c; }
 
 // page-locked room for `len` bytes of text owned by the context: a caller that reads its file straight into it saves the staging copy
 extern "C" char* cto_dev_tokeniser_buffer(cto_dev_tokeniser* c, size_t len) {
-    if (!c || c->pin(&c->h_text, &c->h_text_cap, len + 16) != CTO_OK) return nullptr;
-    return static_cast<char*>(c->h_text);
+    if (!c || c->h_text.ensure(len + 16) != CTO_OK) return nullptr;
+    return c->h_text.as<char>();
 }
 
 extern "C" int cto_tokenise_device(cto_dev_tokeniser* cx, const char* text, size_t len, const char* ref_seq, int64_t ref_start, size_t ref_len,
@@ -748,32 +658,31 @@ extern "C" int cto_tokenise_device(cto_dev_tokeniser* cx, const char* text, size
     // text that does not end in '\n' (or is empty, or would overflow the 32-bit row bookkeeping) is the host reader's
     if (len == 0 || text[len - 1] != '\n' || len >= (size_t(1) << 31)) { *fallback = 1; return CTO_OK; }
     int rc;
-    if (text != cx->h_text) {
-        if ((rc = cx->pin(&cx->h_text, &cx->h_text_cap, len + 16))) return rc;
-        memcpy(cx->h_text, text, len);
+    if (text != cx->h_text.p) {
+        if ((rc = cx->h_text.ensure(len + 16))) return rc;
+        memcpy(cx->h_text.p, text, len);
     }
     const int n_seg = int(cdiv(int64_t(len), SEG));
     if ((rc = cx->text.ensure(len + 128)) || (rc = cx->ref.ensure(ref_len + 16)) || (rc = cx->seg_cnt.ensure(size_t(n_seg) * 4)) ||
-        (rc = cx->seg_base.ensure(size_t(n_seg + 1) * 4)) || (rc = cx->tiles.ensure(size_t(cdiv(std::max<int64_t>(n_seg, int64_t(len / 8)), SCAN_TILE) + 2) * 8)) ||
-        (rc = cx->flags.ensure(sizeof(TokFlags) + 64)) || (rc = cx->pin(&cx->h_stage, &cx->h_stage_cap, 4096)))
+        (rc = cx->seg_base.ensure(size_t(n_seg + 1) * 4)) ||
+        (rc = cx->flags.ensure(sizeof(TokFlags) + 64)) || (rc = cx->h_stage.ensure(4096)))
         return rc;
     CTO_HIP(hipMemsetAsync(cx->text.as<char>() + (len & ~size_t(15)), '\n', 96 + (len & 15), s));     // the readers look up to five words past the end
-    CTO_HIP(hipMemcpyAsync(cx->text.p, cx->h_text, len, hipMemcpyHostToDevice, s));
+    CTO_HIP(hipMemcpyAsync(cx->text.p, cx->h_text.p, len, hipMemcpyHostToDevice, s));
     CTO_HIP(hipMemcpyAsync(cx->ref.p, ref_seq, ref_len, hipMemcpyHostToDevice, s));
     CTO_HIP(hipMemsetAsync(cx->flags.p, 0, sizeof(TokFlags), s));
     TokFlags* fl = cx->flags.as<TokFlags>();
-    auto* hf = static_cast<TokFlags*>(cx->h_stage);
+    auto* hf = cx->h_stage.as<TokFlags>();
     auto fetch_flags = [&]() -> int {
         CTO_HIP(hipMemcpyAsync(hf, fl, sizeof(TokFlags), hipMemcpyDeviceToHost, s));
-        return cx->wait(s);
+        CTO_HIP(record_and_wait(cx->ev, s));
+        return CTO_OK;
     };
     const unsigned char* d_text = cx->text.as<unsigned char>();
     // rows: newline counts per 256-byte segment, one launch for their scan, the row starts
     const int seg_tiles = int(cdiv(n_seg, SCAN_TILE));
-    if ((rc = cx->tiles.ensure(size_t(seg_tiles + 2) * 8))) return rc;
     hipLaunchKernelGGL(k_count_lines, dim3(unsigned(cdiv(int64_t(n_seg) * PIECES, 256))), dim3(256), 0, s, d_text, (long long)len, n_seg, cx->seg_cnt.as<int>());
-    hipLaunchKernelGGL((k_tile_apply<int, true>), dim3(unsigned(seg_tiles)), dim3(256), 0, s, cx->seg_cnt.as<int>(), n_seg, static_cast<const int*>(nullptr),
-                       cx->seg_base.as<int>(), &fl->n_rows);
+    hipLaunchKernelGGL(k_seg_scan, dim3(unsigned(seg_tiles)), dim3(256), 0, s, cx->seg_cnt.as<int>(), n_seg, cx->seg_base.as<int>(), &fl->n_rows);
     CTO_HIP(hipGetLastError());
     if ((rc = fetch_flags())) return rc;
     const int n_rows = hf->n_rows;
@@ -841,14 +750,14 @@ extern "C" int cto_tokenise_device(cto_dev_tokeniser* cx, const char* text, size
                         lite->col_ref.data(), lite->key_off.data()};
         size_t off[7], total = 256;                            // (the flags came down into the first bytes of the same buffer)
         for (int i = 0; i < 7; ++i) { off[i] = total; total += (bytes[i] + 63) / 64 * 64; }
-        if ((rc = cx->pin(&cx->h_stage, &cx->h_stage_cap, total + 64))) return rc;         // (may move the buffer: nothing is in flight into it)
-        char* hs = static_cast<char*>(cx->h_stage);
+        if ((rc = cx->h_stage.ensure(total + 64))) return rc;         // (may move the buffer: nothing is in flight into it)
+        char* hs = cx->h_stage.as<char>();
         const TokFlags* hf2 = reinterpret_cast<const TokFlags*>(hs);
         // slow (a quality character out of range, a separator out of place) and bad_order come down with the tables
         CTO_HIP(hipMemcpyAsync(hs, fl, sizeof(TokFlags), hipMemcpyDeviceToHost, s));
         for (int i = 0; i < 7; ++i)
             if (bytes[i]) CTO_HIP(hipMemcpyAsync(hs + off[i], src[i], bytes[i], hipMemcpyDeviceToHost, s));
-        if ((rc = cx->wait(s))) return rc;
+        CTO_HIP(record_and_wait(cx->ev, s));
         if (hf2->slow || hf2->bad_order) { *fallback = 1; return CTO_OK; }
         for (int i = 0; i < 7; ++i)
             if (bytes[i]) memcpy(dst[i], hs + off[i], bytes[i]);

@@ -42,6 +42,22 @@ def _unpaired_reads(rng, n, ref_lens, skips=False):
     return reads
 
 
+def _indel_dense_reads(rng, n, ref, L):
+    """unpaired reads that carry an insertion or a deletion every 5-25 aligned bases: more than 16 384 distinct indel keys in a
+    region of L positions, so that the key-string offsets take the spread-out scan"""
+    reads = []
+    for i in range(n):
+        cigar = [("M", int(rng.integers(5, 26)))]
+        for _ in range(int(rng.integers(4, 12))):
+            cigar += [(str(rng.choice(["I", "D"])), int(rng.integers(1, 5))), ("M", int(rng.integers(5, 26)))]
+        qlen = sum(k for op, k in cigar if op in "MI")
+        span = sum(k for op, k in cigar if op in "MD")
+        reads.append(dict(name="x%d" % i, flag=int(rng.choice([0, 16])), ref=ref, pos=int(rng.integers(0, L - span)), mapq=60, cigar=cigar,
+                          seq="".join(rng.choice(list("ACGT"), size=qlen)), qual=[int(q) for q in rng.integers(0, 60, size=qlen)], cg_tag=False))
+    reads.sort(key=lambda r: r["pos"])
+    return reads
+
+
 @pytest.mark.parametrize("seed", [1, 2, 3])
 def test_device_pileup_equals_the_host_reader(tmp_path, seed):
     import torch
@@ -53,11 +69,15 @@ def test_device_pileup_equals_the_host_reader(tmp_path, seed):
     refs = [("chrA", ref_lens[0]), ("chrB", ref_lens[1])]
     ref_seqs = ["".join(rng.choice(list("ACGTN"), p=[.24, .24, .24, .24, .04], size=L)) for L in ref_lens]
     reads = _unpaired_reads(rng, 1500, ref_lens)
+    dense = np.random.default_rng(100 + seed)                  # a third contig, its reads dense with indels
+    refs.append(("chrI", 30000))
+    ref_seqs.append("".join(dense.choice(list("ACGT"), size=30000)))
+    reads += _indel_dense_reads(dense, 2500, 2, 30000)
     bam = str(tmp_path / "t.bam")
     write_bam(bam, refs, reads, block_payload=1500 if seed != 3 else 60000)
     cases = [(0, 1, ref_lens[0], None), (0, 5000, 9000, None), (0, 16380, 16400, None), (1, 1, ref_lens[1], None),
              (1, 700, 2400, [(650, 720), (900, 934), (2000, 2500)]), (0, 39000, 40000, [(38990, 39010)]),
-             (0, 2000, 38000, [(k, k + 33) for k in range(2100, 37000, 211)])]
+             (0, 2000, 38000, [(k, k + 33) for k in range(2100, 37000, 211)]), (2, 1, 30000, None)]
     dp = DevicePileup()
     dev = torch.device("cuda:0")
     done = 0
@@ -72,7 +92,8 @@ def test_device_pileup_equals_the_host_reader(tmp_path, seed):
             np.testing.assert_array_equal(got[k], want[k], err_msg="%s %s:%d-%d" % (k, name, start, end))
         assert got["keys"] == want["keys"]
         done += len(want["col_pos"]) > 0
-    assert done >= 6
+    assert done >= 7
+    assert len(want["keys"]) > 16384                           # the last case
 
 
 def test_device_pileup_depth_cap_only_where_it_can_bite(tmp_path):
