@@ -4,7 +4,8 @@ import importlib
 import sys
 
 SUBMODULES = ("extract_candidates_calling", "concat_files", "create_tensor_pileup_calling", "predict", "call_variants", "pileup_call", "call_chunks",
-              "sort_vcf", "postprocess_vcf", "haplotype_filtering", "realign_reads", "realign_variants")
+              "sort_vcf", "postprocess_vcf", "haplotype_filtering", "realign_reads", "realign_variants",
+              "nonsomatic_tagging")
 
 
 def dispatch(name, argv):

@@ -70,6 +70,11 @@ class RealignStats(C.Structure):
                 ("tracebacks", c_i64), ("tracebacks_declined", c_i64), ("traceback_ms", C.c_double)]
 
 
+class PonStats(C.Structure):
+    _fields_ = [("bytes_read", c_i64), ("bytes_inflated", c_i64), ("blocks_device", c_i64), ("records", c_i64), ("host_lines", c_i64),
+                ("used_tbi", c_i32), ("kind", c_i32), ("seconds", C.c_double)]
+
+
 class RunStats(C.Structure):
     _fields_ = [("candidates", c_i64), ("sites", c_i64), ("rows", c_i64), ("low_coverage", c_i64), ("clamped", c_i64), ("seconds", C.c_double),
                 ("produce_s", C.c_double), ("finish_s", C.c_double), ("launch_s", C.c_double), ("launcher_wait_s", C.c_double),
@@ -161,6 +166,12 @@ SYMBOLS = {
     "cto_qual_finalize": (c_i64, [c_vp, c_vp, c_i64]),
     "cto_candidate_positions": (C.c_int, [c_vp, c_vp, C.c_int, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "cto_softmax_probs": (C.c_int, [c_vp, c_vp, C.c_int, c_i64, c_vp, c_vp]),
+    "cto_pon_create": (C.c_int, [C.POINTER(c_vp)]),
+    "cto_pon_destroy": (None, [c_vp]),
+    "cto_pon_set_calls": (C.c_int, [c_vp, C.c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "cto_pon_match_file": (C.c_int, [c_vp, C.c_char_p, C.c_char_p, C.c_int, c_vp, C.POINTER(PonStats), c_vp]),
+    "cto_pon_host_lines": (c_i64, [c_vp, C.POINTER(c_vp), C.POINTER(c_vp), C.POINTER(c_vp)]),
+    "cto_tbi_contig_chunks": (c_i64, [c_vp, C.c_size_t, C.c_char_p, c_vp, c_i64]),
     "cto_posterior_from_probs": (C.c_int, [c_vp, C.c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 

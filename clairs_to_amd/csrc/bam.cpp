@@ -255,26 +255,11 @@ void reg2bins(int64_t beg, int64_t end, std::vector<uint32_t>* bins) {
     for (int k = 4681 + int(beg >> 14); k <= 4681 + int(end >> 14); ++k) bins->push_back(uint32_t(k));
 }
 
-// chunks of reference `tid` that may overlap [beg, end), merged and sorted; false on a malformed index
-bool bai_query(const char* path, int tid, int64_t beg, int64_t end, std::vector<Chunk>* out, std::string* err,
-               std::vector<uint64_t>* linear = nullptr) {
-    FILE* f = fopen(path, "rb");
-    if (!f) { *err = std::string("cannot open index ") + path; return false; }
-    std::vector<uint8_t> buf;
-    off_t sz = -1;
-    if (fseeko(f, 0, SEEK_END) == 0) sz = ftello(f);
-    if (sz < 0 || sz > (off_t(1) << 32) || fseeko(f, 0, SEEK_SET) != 0) {       // not seekable (a pipe, a directory) or absurdly large
-        fclose(f);
-        *err = std::string("cannot read index ") + path;
-        return false;
-    }
-    buf.resize(size_t(sz));
-    const bool ok = fread(buf.data(), 1, buf.size(), f) == buf.size();
-    fclose(f);
-    if (!ok || buf.size() < 8 || memcmp(buf.data(), "BAI\1", 4) != 0) { *err = "not a BAI index"; return false; }
-    size_t o = 4;
+// chunks of reference `tid` that may overlap [beg, end), merged and sorted, from the binning index in `buf` (BAI, or the inflated
+// TBI) whose per-reference records start at byte `o` after its n_ref references; false on a malformed index
+bool index_query(const std::vector<uint8_t>& buf, size_t o, int n_ref, int tid, int64_t beg, int64_t end, std::vector<Chunk>* out,
+                 std::string* err, std::vector<uint64_t>* linear = nullptr) {
     auto need = [&](size_t n) { return o + n <= buf.size(); };
-    const int n_ref = le32(buf.data() + o); o += 4;
     if (tid < 0 || tid >= n_ref) { *err = "reference not in the index"; return false; }
     std::vector<uint32_t> want;
     reg2bins(beg, end, &want);
@@ -318,6 +303,31 @@ bool bai_query(const char* path, int tid, int64_t beg, int64_t end, std::vector<
         else out->push_back(d);
     }
     return true;
+}
+
+bool read_index_file(const char* path, std::vector<uint8_t>* buf, std::string* err) {
+    FILE* f = fopen(path, "rb");
+    if (!f) { *err = std::string("cannot open index ") + path; return false; }
+    off_t sz = -1;
+    if (fseeko(f, 0, SEEK_END) == 0) sz = ftello(f);
+    if (sz < 0 || sz > (off_t(1) << 32) || fseeko(f, 0, SEEK_SET) != 0) {       // not seekable (a pipe, a directory) or absurdly large
+        fclose(f);
+        *err = std::string("cannot read index ") + path;
+        return false;
+    }
+    buf->resize(size_t(sz));
+    const bool ok = fread(buf->data(), 1, buf->size(), f) == buf->size();
+    fclose(f);
+    if (!ok) { *err = std::string("cannot read index ") + path; return false; }
+    return true;
+}
+
+bool bai_query(const char* path, int tid, int64_t beg, int64_t end, std::vector<Chunk>* out, std::string* err,
+               std::vector<uint64_t>* linear = nullptr) {
+    std::vector<uint8_t> buf;
+    if (!read_index_file(path, &buf, err)) return false;
+    if (buf.size() < 8 || memcmp(buf.data(), "BAI\1", 4) != 0) { *err = "not a BAI index"; return false; }
+    return index_query(buf, 8, le32(buf.data() + 4), tid, beg, end, out, err, linear);
 }
 
 // ------------------------------------------------------------------------------------------------ records + pileup
@@ -1108,3 +1118,30 @@ extern "C" int64_t cto_bgzf_scan(const uint8_t* bytes, size_t len, int64_t file_
     *out_bytes = out;
     return n;
 }
+
+// The tabix index (SAM/htslib specification, "TBI"): the same binning index as a BAI behind a header that names the sequences.
+// `tbi` is the index INFLATED (a .tbi file is BGZF).  The chunks that may hold records of contig `ctg` anywhere on it, merged and
+// sorted; *found = false (and no chunks) when the index does not name the contig.
+namespace cto {
+bool tbi_contig_chunks(const uint8_t* tbi, size_t len, const char* ctg, std::vector<IndexChunk>* out, bool* found, std::string* err) {
+    const std::vector<uint8_t> buf(tbi, tbi + len);
+    *found = false;
+    if (len < 36 || memcmp(tbi, "TBI\1", 4) != 0) { *err = "not a tabix index"; return false; }
+    const int n_ref = le32(tbi + 4);
+    const int l_nm = le32(tbi + 32);
+    if (n_ref < 0 || l_nm < 0 || 36 + size_t(l_nm) > len) { *err = "malformed tabix index"; return false; }
+    int tid = -1, i = 0;
+    for (size_t o = 36; o < 36 + size_t(l_nm) && i < n_ref; ++i) {        // NUL-terminated names, in reference-id order
+        const char* nm = reinterpret_cast<const char*>(tbi + o);
+        const size_t n = strnlen(nm, 36 + size_t(l_nm) - o);
+        if (tid < 0 && strlen(ctg) == n && memcmp(nm, ctg, n) == 0) tid = i;
+        o += n + 1;
+    }
+    if (tid < 0) return true;
+    *found = true;
+    std::vector<Chunk> chunks;
+    if (!index_query(buf, 36 + size_t(l_nm), n_ref, tid, 0, int64_t(1) << 29, &chunks, err)) return false;   // the whole contig
+    for (const Chunk& c : chunks) out->push_back(IndexChunk{c.beg, c.end});
+    return true;
+}
+}  // namespace cto

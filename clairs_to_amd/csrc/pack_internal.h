@@ -139,4 +139,7 @@ int pack_from_mpileup_impl(const char* text, size_t len, const char* ref_seq, in
 // streams use (csrc/pipeline.hip: one buffer per chunk slot); csrc/extract.hip
 int extract_candidates_scratch(const cto_pack_view* dp, int min_mq, int min_bq, double snv_min_af, double indel_min_af, double min_coverage,
                                int alt_base_num, int select_indel, uint32_t* scratch, uint8_t* flags, int32_t* depth, void* stream);
+// the chunks of a tabix index (inflated .tbi) that may hold records of contig `ctg` (csrc/bam.cpp, the BAI reader's binning code)
+struct IndexChunk { uint64_t beg, end; };     // virtual offsets: compressed block offset << 16 | offset in the inflated block
+bool tbi_contig_chunks(const uint8_t* tbi, size_t len, const char* ctg, std::vector<IndexChunk>* out, bool* found, std::string* err);
 }  // namespace cto

@@ -650,6 +650,44 @@ int64_t cto_realign_read_evidence(const char* seq, int64_t seq_len, const char* 
 int cto_dbg_consensus(const char* ref, int n_reads, const char* const* reads, const int32_t* lowbq, const int64_t* lowbq_off,
                       char* buf, size_t cap, size_t* used);
 
+/* Panel-of-normals scan on the DEVICE (csrc/pon.hip): the PoN pass of src/nonsomatic_tagging.py (_iter_pon_vcf_records_stream :162-231,
+ * _parse_pon_line :148-160, apply_one :245-264).  The context holds the call set:
+ *   cto_pon_set_calls   n_ctg contig names (ctg_bytes[ctg_off[i], ctg_off[i+1])), per call its contig index, POS and the REF / first ALT
+ *                       strings (str_bytes[str_off[2i], str_off[2i+1]) and [str_off[2i+1], str_off[2i+2])).  Arrays are copied.
+ *   cto_pon_match_file  hit[i] = 1 when a record of the PoN file at `path` matches call i (same contig and POS; with require_allele also
+ *                       REF and one comma-separated ALT, byte for byte), else 0.  only_contig non-NULL = the reference's --ctg_name: only
+ *                       records of that contig count, and a file with a `<path>.tbi` index is read only where the index puts that contig.
+ *                       The file kind follows the reference: a name ending in ".vcf" is text split on '\n'; anything else is what
+ *                       `gzip -dc` prints (BGZF inflated on the device, other gzip on the host, not gzip = no records) split on '\n', '\r'
+ *                       and "\r\n".  Lines the device cannot decide exactly (a byte >= 0x80 in the first five fields or at the end of the
+ *                       stripped line, a POS that is not 1-18 ASCII digits) are not matched here: they are handed back through
+ *                       cto_pon_host_lines (bytes with their line ending, file order, 1-based line numbers of the text scanned - on the
+ *                       .tbi path counted from the first line of the contig's chunks) for the caller to parse with the reference's own
+ *                       rules.  A .tbi that cannot be read or parsed, or that names bytes which are not BGZF, is not used: the whole file
+ *                       is scanned.  Synchronises `stream`. */
+typedef struct cto_pon cto_pon;
+typedef struct cto_pon_stats {
+    int64_t bytes_read;        /* bytes of the PoN file read                                               */
+    int64_t bytes_inflated;    /* bytes of text scanned (after inflation)                                  */
+    int64_t blocks_device;     /* BGZF blocks inflated on the device                                       */
+    int64_t records;           /* lines with at least five fields (after the '#' and strip rules)          */
+    int64_t host_lines;        /* lines handed back to the host (cto_pon_host_lines)                       */
+    int32_t used_tbi;          /* 1: only the contig's chunks of the .tbi were read                        */
+    int32_t kind;              /* 0 plain text (.vcf), 1 BGZF on the device, 2 gzip on the host, 3 not gzip */
+    double  seconds;           /* wall time of the call                                                    */
+} cto_pon_stats;
+int  cto_pon_create(cto_pon** out);
+void cto_pon_destroy(cto_pon* ctx);
+int  cto_pon_set_calls(cto_pon* ctx, int n_ctg, const char* ctg_bytes, const int64_t* ctg_off, int64_t n_calls, const int32_t* call_ctg,
+                       const int64_t* call_pos, const char* str_bytes, const int64_t* str_off);
+int  cto_pon_match_file(cto_pon* ctx, const char* path, const char* only_contig, int require_allele, uint8_t* hit, cto_pon_stats* stats,
+                        void* stream);
+int64_t cto_pon_host_lines(cto_pon* ctx, const char** bytes, const int64_t** off, const int64_t** line_no);
+/* The chunks of a tabix index that cto_pon_match_file reads for contig `ctg` (the binning index of csrc/bam.cpp's BAI reader, whole contig):
+ * tbi_file = the .tbi file's bytes (BGZF); chunks[2i], chunks[2i + 1] = begin / end virtual offsets, merged and sorted.  Returns their number
+ * (0: the index does not name the contig), CTO_ENOMEM when `cap` pairs do not hold them, CTO_EINVAL when the bytes are not a tabix index. */
+int64_t cto_tbi_contig_chunks(const uint8_t* tbi_file, size_t len, const char* ctg, uint64_t* chunks, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif
