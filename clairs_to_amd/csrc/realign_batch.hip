@@ -24,21 +24,17 @@
 // are held byte-equal by tests/test_gpu_realign.py against oracle/_ref (the reference's own realigner.cpp + SSW).
 #include <algorithm>
 #include <atomic>
-#include <chrono>
-#include <pthread.h>
-#include <condition_variable>
 #include <cstring>
-#include <exception>
-#include <functional>
-#include <mutex>
-#include <numeric>
 #include <string>
-#include <thread>
+#include <vector>
 #include "common.h"
+#include "hip_buffers.h"
+#include "realign_host.h"
 #include "realign_internal.h"
 
 using cto_realign::Ends;
 using cto_realign::Window;
+using namespace cto::realign_host;
 
 namespace {
 
@@ -748,274 +744,13 @@ __global__ __launch_bounds__(64) void k_sw(const signed char* pool, const SwDesc
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
-// Device memory of one call: a bump allocator over a block the library keeps between calls (grow-only; one call at a time has the kept
-// one, a concurrent call - or one on another device - a block of its own that it frees).  A call makes ~25 small allocations; as
-// hipMalloc / hipFree pairs they cost it ~3 ms (hipFree waits for the device each time).
-struct DeviceArena {
-    struct Block { char* p; size_t cap, used; };
-    std::vector<Block> blocks;
-    size_t asked = 0;                  // bytes taken since the last reset
-    int device = -1;
-    void* take(size_t bytes) {
-        bytes = (std::max<size_t>(bytes, 1) + 255) & ~size_t(255);
-        asked += bytes;
-        if (!blocks.empty() && blocks.back().used + bytes <= blocks.back().cap) {
-            void* r = blocks.back().p + blocks.back().used;
-            blocks.back().used += bytes;
-            return r;
-        }
-        const size_t cap = std::max<size_t>(bytes, std::max<size_t>(size_t(32) << 20, blocks.empty() ? 0 : 2 * blocks.back().cap));
-        char* p = nullptr;
-        if (hipMalloc(reinterpret_cast<void**>(&p), cap) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        blocks.push_back(Block{p, cap, bytes});
-        return p;
-    }
-    void free_all() { for (Block& b : blocks) (void)hipFree(b.p); blocks.clear(); asked = 0; }
-    // end of a call: one block large enough for what this call took, so that the next one of its size allocates nothing
-    void reset() {
-        if (blocks.size() > 1) {
-            const size_t want = asked + asked / 4;
-            free_all();
-            char* p = nullptr;
-            if (hipMalloc(reinterpret_cast<void**>(&p), want) == hipSuccess) blocks.push_back(Block{p, want, 0});
-            else (void)hipGetLastError();
-        } else if (!blocks.empty()) {
-            blocks.back().used = 0;
-        }
-        asked = 0;
-    }
-};
-// the same for page-locked host memory: what a call copies up and down (operand bytes, descriptors, results) is built in and landed on
-// pinned blocks, so that hipMemcpyAsync is a DMA and not a staged copy through the runtime's bounce buffers
-struct HostArena {
-    struct Block { char* p; size_t cap, used; };
-    std::vector<Block> blocks;
-    size_t asked = 0;
-    void* take(size_t bytes) {
-        bytes = (std::max<size_t>(bytes, 1) + 255) & ~size_t(255);
-        asked += bytes;
-        if (!blocks.empty() && blocks.back().used + bytes <= blocks.back().cap) {
-            void* r = blocks.back().p + blocks.back().used;
-            blocks.back().used += bytes;
-            return r;
-        }
-        const size_t cap = std::max<size_t>(bytes, std::max<size_t>(size_t(16) << 20, blocks.empty() ? 0 : 2 * blocks.back().cap));
-        char* p = nullptr;
-        if (hipHostMalloc(reinterpret_cast<void**>(&p), cap, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        blocks.push_back(Block{p, cap, bytes});
-        return p;
-    }
-    bool owns(const void* q) const {
-        for (const Block& b : blocks) if (q >= b.p && q < b.p + b.cap) return true;
-        return false;
-    }
-    void free_all() { for (Block& b : blocks) (void)hipHostFree(b.p); blocks.clear(); asked = 0; }
-    void reset() {
-        if (blocks.size() > 1) {
-            const size_t want = asked + asked / 4;
-            free_all();
-            char* p = nullptr;
-            if (hipHostMalloc(reinterpret_cast<void**>(&p), want, hipHostMallocDefault) == hipSuccess) blocks.push_back(Block{p, want, 0});
-            else (void)hipGetLastError();
-        } else if (!blocks.empty()) {
-            blocks.back().used = 0;
-        }
-        asked = 0;
-    }
-};
-thread_local HostArena* t_harena = nullptr;
-// std::vector over the call's pinned arena (plain heap outside a call or when the arena cannot grow)
-template <class T>
-struct PinnedAlloc {
-    typedef T value_type;
-    PinnedAlloc() = default;
-    template <class U> PinnedAlloc(const PinnedAlloc<U>&) {}
-    T* allocate(size_t n) {
-        if (t_harena) { void* p = t_harena->take(n * sizeof(T)); if (p) return static_cast<T*>(p); }
-        return static_cast<T*>(::operator new(n * sizeof(T)));
-    }
-    void deallocate(T* p, size_t) { if (!(t_harena && t_harena->owns(p))) ::operator delete(p); }
-    template <class U> bool operator==(const PinnedAlloc<U>&) const { return true; }
-    template <class U> bool operator!=(const PinnedAlloc<U>&) const { return false; }
-};
-template <class T> using pinned_vector = std::vector<T, PinnedAlloc<T>>;
-
-thread_local DeviceArena* t_arena = nullptr;
-struct ArenaLease {
-    static std::mutex& lock() { static std::mutex m; return m; }
-    static DeviceArena& kept() { static DeviceArena a; return a; }
-    static HostArena& kept_host() { static HostArena a; return a; }
-    static bool& busy() { static bool b = false; return b; }
-    DeviceArena* a = nullptr;
-    DeviceArena* prev = nullptr;
-    HostArena* h = nullptr;
-    HostArena* hprev = nullptr;
-    bool from_kept = false;
-    ArenaLease() {
-        int dev = -1;
-        (void)hipGetDevice(&dev);
-        {
-            std::lock_guard<std::mutex> g(lock());
-            if (!busy() && (kept().device < 0 || kept().device == dev)) { busy() = true; kept().device = dev; a = &kept(); from_kept = true; }
-        }
-        if (!a) a = new DeviceArena();
-        h = from_kept ? &kept_host() : new HostArena();
-        prev = t_arena; hprev = t_harena;
-        t_arena = a; t_harena = h;
-    }
-    ~ArenaLease() {
-        t_arena = prev; t_harena = hprev;
-        if (from_kept) { a->reset(); h->reset(); std::lock_guard<std::mutex> g(lock()); busy() = false; }
-        else { a->free_all(); delete a; h->free_all(); delete h; }
-    }
-};
-
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    bool owned = true;                 // false: the call's arena owns the bytes
-    ~DevBuf() { if (p && owned) (void)hipFree(p); }
-    int alloc(size_t n) {
-        if (t_arena) {
-            p = static_cast<T*>(t_arena->take(std::max<size_t>(n, 1) * sizeof(T)));
-            owned = false;
-            CTO_REQUIRE(p != nullptr, CTO_EHIP, "cto_realign_windows: out of device memory");
-            return CTO_OK;
-        }
-        CTO_HIP(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 1) * sizeof(T)));
-        return CTO_OK;
-    }
-    template <class A>
-    int put(const std::vector<T, A>& v, hipStream_t s) {
-        int rc = alloc(v.size());
-        if (rc != CTO_OK) return rc;
-        if (!v.empty()) CTO_HIP(hipMemcpyAsync(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
-        return CTO_OK;
-    }
-    void swap(DevBuf& o) { std::swap(p, o.p); std::swap(owned, o.owned); }
-};
-
-double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-// Worker threads that outlive a call.  A call runs a dozen parallel loops over its windows (packing, collecting pairs, filing results,
-// planning and composing tracebacks) of a millisecond or less each; as std::threads created and joined per loop, sixteen at a time, the
-// creation alone was a third of a millisecond per loop.  The pool is made once (grown on demand, never destroyed: its threads sleep on a
-// condition variable and end with the process); one call at a time uses it, a concurrent one falls back to threads of its own.
-class WorkerPool {
-    std::mutex m;
-    std::condition_variable cv_start, cv_done;
-    std::vector<std::thread> th;
-    const std::function<void()>* job = nullptr;
-    unsigned long long gen = 0;
-    int want = 0, pending = 0;
-    void worker(int id) {
-        unsigned long long seen = 0;
-        for (;;) {
-            const std::function<void()>* mine = nullptr;
-            {
-                std::unique_lock<std::mutex> lk(m);
-                cv_start.wait(lk, [&] { return gen != seen; });
-                seen = gen;
-                if (id < want) mine = job;
-            }
-            if (!mine) continue;
-            (*mine)();
-            std::lock_guard<std::mutex> lk(m);
-            if (--pending == 0) cv_done.notify_all();
-        }
-    }
-public:
-    std::mutex use;                                    // held by the call that runs loops on the pool
-    bool run(int helpers, const std::function<void()>& f) {
-        try {
-            std::lock_guard<std::mutex> lk(m);
-            while (int(th.size()) < helpers) { th.emplace_back(&WorkerPool::worker, this, int(th.size())); th.back().detach(); }
-        } catch (...) {
-            return false;                              // no more threads to be had
-        }
-        {
-            std::lock_guard<std::mutex> lk(m);
-            job = &f; want = helpers; pending = helpers; ++gen;
-        }
-        cv_start.notify_all();
-        f();
-        std::unique_lock<std::mutex> lk(m);
-        cv_done.wait(lk, [&] { return pending == 0; });
-        job = nullptr;
-        return true;
-    }
-    // (a child of fork() has none of the parent's threads: it starts with a pool of its own; the parent's object is left as it is)
-    static WorkerPool*& slot() { static WorkerPool* p = nullptr; return p; }
-    static WorkerPool& get() {
-        static std::once_flag once;
-        std::call_once(once, [] { (void)pthread_atfork(nullptr, nullptr, [] { slot() = new WorkerPool(); }); slot() = new WorkerPool(); });
-        return *slot();
-    }
-};
-
-template <class F>
-void parallel_for(size_t n, int threads, F&& f) {
-    // an exception on a worker (std::bad_alloc in a window's vectors) must not reach std::terminate: the first one is kept, every
-    // worker stops taking items, and the caller rethrows it after the join - where the C boundary's CTO_CATCH turns it into an error code
-    std::atomic<size_t> next{0};
-    std::atomic<bool> failed{false};
-    std::exception_ptr first;
-    std::mutex first_lock;
-    const std::function<void()> work = [&]() {
-        try {
-            for (size_t i = next++; i < n && !failed.load(std::memory_order_relaxed); i = next++) f(i);
-        } catch (...) {
-            std::lock_guard<std::mutex> g(first_lock);
-            if (!first) first = std::current_exception();
-            failed.store(true);
-        }
-    };
-    const int nt = int(std::min<size_t>(size_t(std::max(1, threads)), n));
-    bool done = false;
-    if (nt > 1) {
-        WorkerPool& pool = WorkerPool::get();
-        std::unique_lock<std::mutex> mine(pool.use, std::try_to_lock);
-        if (mine.owns_lock()) done = pool.run(nt - 1, work);
-    }
-    if (!done) {
-        std::vector<std::thread> own;
-        try {
-            for (int t = 1; t < nt; ++t) own.emplace_back(work);
-        } catch (...) {                               // no more threads to be had: the ones that started and this one do the work
-        }
-        work();
-        for (std::thread& t : own) t.join();
-    }
-    if (first) std::rethrow_exception(first);
-}
-
-struct Reaper {
-    std::mutex m;
-    std::thread t;
-    void wait() { if (t.joinable()) t.join(); }
-    ~Reaper() { wait(); }
-};
-Reaper g_reaper;
-void reap(std::vector<Window>&& ws) {
-    std::lock_guard<std::mutex> lock(g_reaper.m);
-    g_reaper.wait();
-    auto* gone = new std::vector<Window>(std::move(ws));
-    g_reaper.t = std::thread([gone]() { delete gone; });
-}
-
+// Host driver of the three device stages (its plumbing - arenas, kept objects, events, worker threads - is realign_host.h)
 bool device_eligible(const Window& w) {
     if (w.reference.size() > size_t(FP_LMAX) || w.haps.empty()) return false;
     for (const std::string& h : w.haps) if (h.size() > size_t(FP_LMAX)) return false;
     for (const std::string& r : w.reads) if (r.size() > size_t(FP_RMAX)) return false;
     return true;
 }
-
-// CTO_REALIGN_TRACE=1: the classes of the Smith-Waterman stage and the wall time of every stage of a call, on stderr
-bool trace_on() { static const bool on = std::getenv("CTO_REALIGN_TRACE") != nullptr; return on; }
-struct StageClock {
-    double t = now_ms();
-    void lap(const char* what) { if (trace_on()) { const double n = now_ms(); std::fprintf(stderr, "[realign] %-28s %8.3f ms\n", what, n - t); t = n; } }
-};
 
 int fast_pass_device(std::vector<Window*>& ws, hipStream_t s, int threads, cto_realign_stats* st) {
     StageClock clk;
@@ -1065,9 +800,9 @@ int fast_pass_device(std::vector<Window*>& ws, hipStream_t s, int threads, cto_r
     const int nh = int(hap_win.size());
     if (nh == 0) return CTO_OK;
     clk.lap("  fast pass: pack");
-    DevBuf<unsigned char> d_hap, d_read, d_isref;
-    DevBuf<int> d_hap_off, d_hap_win, d_read_off, d_win_read0, d_prefix, d_suffix, d_hit_score, d_hit_pos, d_hap_score;
-    DevBuf<long long> d_hit_off;
+    ArenaBuf<unsigned char> d_hap, d_read, d_isref;
+    ArenaBuf<int> d_hap_off, d_hap_win, d_read_off, d_win_read0, d_prefix, d_suffix, d_hit_score, d_hit_pos, d_hap_score;
+    ArenaBuf<long long> d_hit_off;
     int rc;
     if ((rc = d_hap.put(hap_bytes, s)) || (rc = d_read.put(read_bytes, s)) || (rc = d_isref.put(hap_isref, s)) || (rc = d_hap_off.put(hap_off, s)) ||
         (rc = d_hap_win.put(hap_win, s)) || (rc = d_read_off.put(read_off, s)) || (rc = d_win_read0.put(win_read0, s)) ||
@@ -1077,8 +812,8 @@ int fast_pass_device(std::vector<Window*>& ws, hipStream_t s, int threads, cto_r
     clk.lap("  fast pass: alloc + H2D");
     FpArgs a{d_hap.p, d_hap_off.p, d_hap_win.p, d_isref.p, d_hit_off.p, d_read.p, d_read_off.p, d_win_read0.p, d_prefix.p, d_suffix.p,
              d_hit_score.p, d_hit_pos.p, d_hap_score.p};
-    hipEvent_t e0, e1;
-    CTO_HIP(hipEventCreate(&e0)); CTO_HIP(hipEventCreate(&e1));
+    Event e0, e1;
+    if ((rc = e0.create()) || (rc = e1.create())) return rc;
     CTO_HIP(hipEventRecord(e0, s));
     hipLaunchKernelGGL(k_fast_pass, dim3(unsigned(nh)), dim3(FP_NT), 0, s, a);
     CTO_HIP(hipGetLastError());
@@ -1093,7 +828,6 @@ int fast_pass_device(std::vector<Window*>& ws, hipStream_t s, int threads, cto_r
     CTO_HIP(hipStreamSynchronize(s));
     float ms = 0.f;
     CTO_HIP(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     if (st) { st->fast_pass_ms += ms; st->fast_pairs += hits; }
     clk.lap("  fast pass: kernel + D2H");
     std::vector<size_t> hfirst(ws.size() + 1, 0);
@@ -1110,15 +844,11 @@ int launch_sw(hipStream_t s, const signed char* pool, const SwDesc* desc, const 
               int Rcap, int Qcap) {
     if (n == 0) return CTO_OK;
     constexpr int LW = BYTE ? 16 : 8;
-    // A pass is a chain of dependent steps: a wavefront runs it at the pace of ONE row whatever the number of rows it holds, so a
-    // class with few alignments (the haplotype-length one: ~2 500 of the bench's batch) can spread them over more wavefronts - rows per
-    // wavefront halve until the class has CTO_SW_MIN_WAVES wavefronts or one row per wavefront.  Round 5 measured 0 -> 17.4 ms, 256 / 512
-    // -> 15.5, 1 024 -> 17.3, 2 048 -> 24.5 and used 512.  Round 6, after the best-cell search stopped re-reading the whole stripe in
-    // every column of a matching pair (the longest class's 16-bit launch: 10.6 -> 7.0 ms), the stage is bound by instruction issue and a
-    // wavefront with idle lanes costs the others its slots: 0 -> 10.1-10.3 ms, 256 -> 10.9, 512 -> 11.2 - full wavefronts are the default
+    // Full wavefronts, however few alignments a class has.  A pass is a chain of dependent steps that a wavefront runs at the pace of
+    // ONE row, so a minimum number of wavefronts per class was tried (rows per wavefront halved until a class had 256 or 512 of them):
+    // the stage is bound by instruction issue and a wavefront with idle lanes costs the others its slots - 10.9 and 11.2 ms against
+    // 10.1-10.3 for the bench's batch.
     int ROWS = 64 / LW;
-    static const int min_waves = std::getenv("CTO_SW_MIN_WAVES") ? atoi(std::getenv("CTO_SW_MIN_WAVES")) : 0;
-    while (ROWS > 1 && (n + ROWS - 1) / ROWS < min_waves) ROWS /= 2;
     (void)Rcap;
     Qcap = (Qcap + 15) & ~15;
     const int segcap = (Qcap + LW - 1) / LW;
@@ -1137,10 +867,10 @@ int launch_sw(hipStream_t s, const signed char* pool, const SwDesc* desc, const 
             if (dev >= 0 && dev < 64) done[dev].store(1, std::memory_order_release);
         }
     }
-    // stripes of 17 .. 128 positions: the register form (row_pass_regs) - the LDS holds the profile only
-    static const bool regs_on = !(std::getenv("CTO_SW_REGS") && atoi(std::getenv("CTO_SW_REGS")) == 0);
-    static const int regs_min = std::getenv("CTO_SW_REGS_MIN") ? atoi(std::getenv("CTO_SW_REGS_MIN")) : 0;
-    if (regs_on && segcap > regs_min && segcap <= 128 && ROWS == 64 / LW) {
+    // stripes of up to 128 positions: the register form (row_pass_regs) - the LDS holds the profile only.  Against the LDS form for
+    // everything the stage went 8.9 -> 8.4 ms with the long stripes in registers and 6.0 -> 5.6 ms with the short ones (16 positions
+    // and fewer) as well, so there is no lower bound and no way back.  (A class of empty queries has no stripe: the LDS form.)
+    if (segcap > 0 && segcap <= 128 && ROWS == 64 / LW) {
         const size_t pm = size_t(sw_sp(segcap)) * LW * sizeof(short) * ROWS;
         const dim3 grid(unsigned((n + ROWS - 1) / ROWS)), block(unsigned(LW * ROWS));
         if (segcap <= 4) hipLaunchKernelGGL((k_sw_regs<BYTE, 1, 4>), grid, block, pm, s, pool, desc, order, n, out, overflowed, segcap);
@@ -1158,63 +888,10 @@ int launch_sw(hipStream_t s, const signed char* pool, const SwDesc* desc, const 
     return CTO_OK;
 }
 
-// Side streams kept between calls (per device; one call at a time holds them, a concurrent call makes and destroys its own): creating and
-// destroying four streams and their events cost a call ~1 ms.
-struct SideStreams {
-    static constexpr int kMax = 5;
-    hipStream_t sx[kMax] = {};
-    hipEvent_t join[kMax] = {};
-    int n = 0;
-    bool cached = false;
-    static std::mutex& lock() { static std::mutex m; return m; }
-    struct Kept { hipStream_t sx[kMax]; hipEvent_t join[kMax]; int n = 0; int device = -1; bool busy = false; };
-    static Kept& kept() { static Kept k; return k; }
-    // stream i (made on first use)
-    int get(int i, hipStream_t* out) {
-        if (i >= kMax) return CTO_EINVAL;
-        while (n <= i) {
-            // at the device's highest priority: the runtime keeps a pool of hardware queues PER PRIORITY and hands a new stream the least used
-            // queue of its pool - beside a process's ordinary streams (torch's, the pipeline's) two of these could land on one queue and their
-            // classes would run one after the other (bench.py's process: 7.2 ms for the stage the stand-alone tool runs in 5.6); a pool of their own
-            // gives the four of them a queue each
-            int lo = 0, hi = 0;
-            if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) { (void)hipGetLastError(); lo = hi = 0; }
-            if (hipStreamCreateWithPriority(&sx[n], hipStreamNonBlocking, hi) != hipSuccess) return CTO_EHIP;
-            if (hipEventCreateWithFlags(&join[n], hipEventDisableTiming) != hipSuccess) { (void)hipStreamDestroy(sx[n]); return CTO_EHIP; }
-            ++n;
-        }
-        *out = sx[i];
-        return CTO_OK;
-    }
-    SideStreams() {
-        int dev = -1;
-        (void)hipGetDevice(&dev);
-        std::lock_guard<std::mutex> g(lock());
-        Kept& k = kept();
-        if (!k.busy && (k.device < 0 || k.device == dev)) {
-            k.busy = true; k.device = dev; cached = true;
-            n = k.n;
-            for (int i = 0; i < n; ++i) { sx[i] = k.sx[i]; join[i] = k.join[i]; }
-        }
-    }
-    ~SideStreams() {
-        for (int i = 0; i < n; ++i) (void)hipStreamSynchronize(sx[i]);
-        if (cached) {
-            std::lock_guard<std::mutex> g(lock());
-            Kept& k = kept();
-            k.n = n;
-            for (int i = 0; i < n; ++i) { k.sx[i] = sx[i]; k.join[i] = join[i]; }
-            k.busy = false;
-        } else {
-            for (int i = 0; i < n; ++i) { (void)hipStreamDestroy(sx[i]); (void)hipEventDestroy(join[i]); }
-        }
-    }
-};
-
 // Both passes of every alignment of `desc` (operands = base codes in `pool`): the end points, in desc order
 template <class PoolVec>
 int sw_ends_pool(const PoolVec& pool, const std::vector<SwDesc>& desc, hipStream_t s, cto_realign_stats* st, std::vector<Ends>& ends,
-                 DevBuf<signed char>* keep_pool = nullptr) {
+                 ArenaBuf<signed char>* keep_pool = nullptr) {
     StageClock clk;
     const int n = int(desc.size());
     ends.assign(static_cast<size_t>(n), Ends{0, 0, 0, 0, 0, 16});
@@ -1223,12 +900,10 @@ int sw_ends_pool(const PoolVec& pool, const std::vector<SwDesc>& desc, hipStream
     // and the footprint is what bounds the wavefronts a CU holds - one class for everything would run the 100-base reads at the
     // occupancy of the haplotype-length queries.  Inside a class by descending work, so that the rows of a wavefront - and the
     // waves of a round - run for about as long.
-    constexpr int kClasses = 11;
-    // (CTO_SW_FINE_CLASSES: eleven classes in steps of 1.5 - smaller LDS footprints, more launches: measured slower, 17-19.5 ms against 15.3)
-    static const bool fine = std::getenv("CTO_SW_FINE_CLASSES") != nullptr;
-    const int qcap_fine[kClasses] = {64, 96, 128, 192, 256, 384, FP_RMAX, 768, 1024, 1536, 0x7fffffff};
-    const int qcap_coarse[kClasses] = {64, 128, 256, FP_RMAX, 0x7fffffff, 0x7fffffff, 0x7fffffff, 0x7fffffff, 0x7fffffff, 0x7fffffff, 0x7fffffff};
-    const int* qcap = fine ? qcap_fine : qcap_coarse;
+    // (Eleven finer classes, in steps of 1.5 from 64 to 1 536, were tried: smaller LDS footprints but more launches - 17-19.5 ms
+    // for the stage against 15.3 with these five.)
+    constexpr int qcap[] = {64, 128, 256, FP_RMAX, 0x7fffffff};
+    constexpr int kClasses = int(sizeof(qcap) / sizeof(qcap[0]));
     std::vector<int> cls[kClasses];
     int Rc[kClasses] = {}, Qc[kClasses] = {};
     long long cells = 0;
@@ -1266,11 +941,11 @@ int sw_ends_pool(const PoolVec& pool, const std::vector<SwDesc>& desc, hipStream
                          desc[v.back()].R, desc[v.back()].Q);
         }
     }
-    DevBuf<signed char> d_pool;
-    DevBuf<SwDesc> d_desc;
-    DevBuf<int> d_order;
-    DevBuf<Ends> d_out;
-    DevBuf<unsigned char> d_ovf;
+    ArenaBuf<signed char> d_pool;
+    ArenaBuf<SwDesc> d_desc;
+    ArenaBuf<int> d_order;
+    ArenaBuf<Ends> d_out;
+    ArenaBuf<unsigned char> d_ovf;
     int rc;
     if ((rc = d_pool.put(pool, s)) || (rc = d_desc.put(desc, s)) || (rc = d_order.put(order, s)) || (rc = d_out.alloc(size_t(n))) ||
         (rc = d_ovf.alloc(size_t(n))))
@@ -1279,14 +954,12 @@ int sw_ends_pool(const PoolVec& pool, const std::vector<SwDesc>& desc, hipStream
     // 8-bit passes, then the 16-bit passes of what overflowed (same slots, same order: a row without overflow leaves at once).  The
     // classes are independent chains of two launches each and every one ends in a tail (the longest alignment of the class), so each
     // runs on a stream of its own, longest queries first.
-    hipEvent_t e0, e1, fork;
-    SideStreams side;
-    CTO_HIP(hipEventCreate(&e0)); CTO_HIP(hipEventCreate(&e1));
-    CTO_HIP(hipEventCreateWithFlags(&fork, hipEventDisableTiming));
+    Event e0, e1, fork;
+    SideStreams side;                                  // (after the buffers and events: it drains the side streams before they go)
+    if ((rc = e0.create()) || (rc = e1.create()) || (rc = fork.create(hipEventDisableTiming))) return rc;
     CTO_HIP(hipEventRecord(e0, s));
     CTO_HIP(hipEventRecord(fork, s));
     int made = 0, used = 0;
-    rc = CTO_OK;
     // at most FOUR streams, the caller's included: the runtime has four hardware queues for a process's streams, and one more stream shares
     // one - its launches then wait behind another class's two launches instead of running beside them (measured: the two shortest classes
     // started when the longest one's 16-bit launch ended, 3 ms of the stage's 8.5 - and again, late in round 6, with four side streams beside
@@ -1307,15 +980,11 @@ int sw_ends_pool(const PoolVec& pool, const std::vector<SwDesc>& desc, hipStream
         if ((rc = launch_sw<true>(t, d_pool.p, d_desc.p, d_order.p + at[c], m, d_out.p, d_ovf.p, Rc[c], Qc[c])) ||
             (rc = launch_sw<false>(t, d_pool.p, d_desc.p, d_order.p + at[c], m, d_out.p, d_ovf.p, Rc[c], Qc[c])))
             break;
-        if (own && hipEventRecord(side.join[made - 1], t) != hipSuccess) rc = CTO_EHIP;
+        if (own && hipEventRecord(side.join(made - 1), t) != hipSuccess) rc = CTO_EHIP;
     }
     for (int i = 0; i < made && rc == CTO_OK; ++i)
-        if (hipStreamWaitEvent(s, side.join[i], 0) != hipSuccess) rc = CTO_EHIP;
-    auto drop = [&]() {
-        for (int i = 0; i < made; ++i) (void)hipStreamSynchronize(side.sx[i]);      // (the streams themselves go back to the cache with `side`)
-        (void)hipEventDestroy(fork);
-    };
-    if (rc != CTO_OK) { drop(); (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return rc; }
+        if (hipStreamWaitEvent(s, side.join(i), 0) != hipSuccess) rc = CTO_EHIP;
+    if (rc != CTO_OK) return rc;
     CTO_HIP(hipEventRecord(e1, s));
     pinned_vector<Ends> landed(static_cast<size_t>(n));
     CTO_HIP(hipMemcpyAsync(landed.data(), d_out.p, size_t(n) * sizeof(Ends), hipMemcpyDeviceToHost, s));
@@ -1323,15 +992,13 @@ int sw_ends_pool(const PoolVec& pool, const std::vector<SwDesc>& desc, hipStream
     memcpy(ends.data(), landed.data(), size_t(n) * sizeof(Ends));
     float ms = 0.f;
     CTO_HIP(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    drop();
     if (st) { st->sw_ms += ms; st->sw_pairs += n; st->sw_cells += cells; }
     if (keep_pool) keep_pool->swap(d_pool);
     clk.lap("  SW: launches + D2H");
     return CTO_OK;
 }
 
-struct SwStage { std::vector<SwDesc> desc; std::vector<size_t> first; DevBuf<signed char> d_pool; };     // what the traceback stage re-uses
+struct SwStage { std::vector<SwDesc> desc; std::vector<size_t> first; ArenaBuf<signed char> d_pool; };     // what the traceback stage re-uses
 
 int ends_device(std::vector<Window*>& ws, hipStream_t s, int threads, cto_realign_stats* st, SwStage& stage) {
     StageClock clk;
@@ -1532,43 +1199,6 @@ __global__ __launch_bounds__(64) void k_banded(const signed char* __restrict__ p
     o.status = status; o.n_runs = nr; o.band = band;
 }
 
-// grow-only direction scratch kept by the library between calls
-struct DirScratch {
-    static std::mutex& lock() { static std::mutex m; return m; }
-    static unsigned char*& kept() { static unsigned char* p = nullptr; return p; }
-    static size_t& kept_cap() { static size_t c = 0; return c; }
-    static bool& busy() { static bool b = false; return b; }
-    static int& kept_device() { static int d = -1; return d; }
-    unsigned char* p = nullptr;
-    bool from_kept = false;
-    bool get(size_t bytes) {
-        bytes = std::max<size_t>(bytes, 1);
-        int dev = -1;
-        (void)hipGetDevice(&dev);
-        {
-            // the kept buffer belongs to the device of the first call (as the kept arena does): a call on another device allocates its own
-            std::lock_guard<std::mutex> g(lock());
-            if (!busy() && (kept_device() < 0 || kept_device() == dev)) {
-                kept_device() = dev;
-                if (kept_cap() < bytes) {
-                    if (kept()) (void)hipFree(kept());
-                    kept() = nullptr; kept_cap() = 0;
-                    const size_t want = bytes + bytes / 4;
-                    if (hipMalloc(reinterpret_cast<void**>(&kept()), want) == hipSuccess) kept_cap() = want;
-                    else { (void)hipGetLastError(); kept() = nullptr; }
-                }
-                if (kept()) { busy() = true; from_kept = true; p = kept(); return true; }
-            }
-        }
-        if (hipMalloc(reinterpret_cast<void**>(&p), bytes) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return false; }
-        return true;
-    }
-    ~DirScratch() {
-        if (from_kept) { std::lock_guard<std::mutex> g(lock()); busy() = false; }
-        else if (p) (void)hipFree(p);
-    }
-};
-
 constexpr int kBandMax = 1024;                          // bands beyond are the host's
 constexpr size_t kDirMax = size_t(6) << 30;             // direction scratch of one call
 
@@ -1603,32 +1233,33 @@ int traceback_pool(const signed char* d_pool, const std::vector<TbDesc>& desc, s
     for (int k = 0; k < n; ++k) order[size_t(k)] = int(keys[size_t(k)] & 0xffffffull);
     int n_wide = 0, cap_wide = 0;
     for (int k = 0; k < n; ++k) if (wide(k)) { ++n_wide; cap_wide = std::max(cap_wide, desc[size_t(k)].band_cap); }
-    DevBuf<TbDesc> d_desc;
-    DevBuf<int> d_order;
-    DevBuf<TbOut> d_out;
+    ArenaBuf<TbDesc> d_desc;
+    ArenaBuf<int> d_order;
+    ArenaBuf<TbOut> d_out;
     int rc;
-    // the direction scratch is the one large allocation of a call (~40 KB per haplotype traceback): kept between calls (one call at a
-    // time uses the kept one, a concurrent call allocates its own); without it every traceback is the host's
-    DirScratch dir_scratch;
-    if (!dir_scratch.get(dir_bytes)) {
+    // the direction scratch is the one large allocation of a call (~40 KB per haplotype traceback): grow-only and kept between calls
+    // (one call at a time uses the kept one, a concurrent call allocates its own); without it every traceback is the host's - which
+    // is no failure: neither the runtime's sticky error nor this thread's last error message is left behind
+    Kept<cto::DevBuf>::Lease dir_scratch;
+    const std::string last_error = cto_last_error();
+    if (dir_scratch->ensure(std::max<size_t>(dir_bytes, 1)) != CTO_OK) {
+        (void)hipGetLastError();
+        cto::set_error("%s", last_error.c_str());
         out.assign(static_cast<size_t>(n), TbOut{});
         for (TbOut& o : out) o.status = 2;
         return CTO_OK;
     }
-    struct { unsigned char* p; } d_dir{dir_scratch.p};
+    unsigned char* const d_dir = dir_scratch->as<unsigned char>();
     if (trace_on()) std::fprintf(stderr, "[realign]   traceback: %d alignments, %.1f MB of direction scratch\n", n, double(dir_bytes) / 1e6);
     if ((rc = d_desc.put(desc, s)) || (rc = d_order.put(order, s)) || (rc = d_out.alloc(size_t(n)))) return rc;
-    hipEvent_t e0, e1;
-    CTO_HIP(hipEventCreate(&e0)); CTO_HIP(hipEventCreate(&e1));
+    Event e0, e1, fork;
+    SideStreams side;                                  // (after the buffers and events: it drains the side stream before they go)
+    if ((rc = e0.create()) || (rc = e1.create())) return rc;
     CTO_HIP(hipEventRecord(e0, s));
     // the few wide-band alignments are a tail of their own: on a second stream beside the many narrow ones
     hipStream_t s2 = nullptr;
-    hipEvent_t fork = nullptr, join = nullptr;
-    SideStreams side;                                  // (declared before the launches: its destructor waits for the side stream)
     if (n_wide > 0 && n_wide < n) {
-        if ((rc = side.get(0, &s2)) != CTO_OK) return rc;
-        join = side.join[0];
-        CTO_HIP(hipEventCreateWithFlags(&fork, hipEventDisableTiming));
+        if ((rc = side.get(0, &s2)) || (rc = fork.create(hipEventDisableTiming))) return rc;
         CTO_HIP(hipEventRecord(fork, s)); CTO_HIP(hipStreamWaitEvent(s2, fork, 0));
     }
     hipStream_t s_wide = s2 ? s2 : s;
@@ -1636,28 +1267,20 @@ int traceback_pool(const signed char* d_pool, const std::vector<TbDesc>& desc, s
         if (count == 0) return CTO_OK;
         const int W = 2 * cap + 4;
         hipLaunchKernelGGL(k_banded, dim3(unsigned(count)), dim3(64), size_t(3) * W * sizeof(int), t, d_pool, d_desc.p, d_order.p + first, count,
-                           d_dir.p, d_out.p, W);
+                           d_dir, d_out.p, W);
         CTO_HIP(hipGetLastError());
         return CTO_OK;
     };
     rc = launch_on(s_wide, 0, n_wide, cap_wide);
     if (rc == CTO_OK) rc = launch_on(s, n_wide, n - n_wide, 62);
-    if (s2) {
-        if (rc == CTO_OK && (hipEventRecord(join, s2) != hipSuccess || hipStreamWaitEvent(s, join, 0) != hipSuccess)) rc = CTO_EHIP;
-        if (rc != CTO_OK) (void)hipStreamSynchronize(s2);
-    }
-    auto drop = [&]() {
-        if (s2) { (void)hipStreamSynchronize(s2); (void)hipEventDestroy(fork); s2 = nullptr; }
-    };
-    if (rc != CTO_OK) { drop(); (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return rc; }
+    if (s2 && rc == CTO_OK && (hipEventRecord(side.join(0), s2) != hipSuccess || hipStreamWaitEvent(s, side.join(0), 0) != hipSuccess)) rc = CTO_EHIP;
+    if (rc != CTO_OK) return rc;
     CTO_HIP(hipEventRecord(e1, s));
     out.resize(static_cast<size_t>(n));
     CTO_HIP(hipMemcpyAsync(out.data(), d_out.p, size_t(n) * sizeof(TbOut), hipMemcpyDeviceToHost, s));
     CTO_HIP(hipStreamSynchronize(s));
     float ms = 0.f;
     CTO_HIP(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    drop();
     if (st) { st->traceback_ms += ms; st->tracebacks += n; }
     return CTO_OK;
 }
@@ -1759,7 +1382,7 @@ extern "C" int cto_ssw_align_batch(int n, const int8_t* codes, size_t n_codes, c
         hipStream_t s = static_cast<hipStream_t>(stream);
         const std::vector<signed char> pool(reinterpret_cast<const signed char*>(codes), reinterpret_cast<const signed char*>(codes) + n_codes);
         std::vector<Ends> ends;
-        DevBuf<signed char> d_pool;
+        ArenaBuf<signed char> d_pool;
         int rc = sw_ends_pool(pool, d, s, nullptr, ends, &d_pool);
         if (rc != CTO_OK) return rc;
         std::vector<cto_realign::TraceJob> jobs(static_cast<size_t>(n));
@@ -1842,12 +1465,9 @@ extern "C" int cto_realign_windows(int n_jobs, cto_realign_job* jobs, int where,
         rc = ends_device(dev, s, threads, stats, stage);
         if (rc != CTO_OK) return rc;
         clk.lap("SW ends (device, copies)");
-        static const bool host_traceback = std::getenv("CTO_REALIGN_HOST_TRACEBACK") != nullptr;      // A/B switch: every traceback in finish()
-        if (!host_traceback) {
-            rc = traceback_device(dev, stage, s, threads, stats);
-            if (rc != CTO_OK) return rc;
-            clk.lap("tracebacks (device, copies)");
-        }
+        rc = traceback_device(dev, stage, s, threads, stats);
+        if (rc != CTO_OK) return rc;
+        clk.lap("tracebacks (device, copies)");
     }
     const double t1 = now_ms();
     // CTO_REALIGN_PLAN_HOST=1 (tests): the host windows' tracebacks go the way the device stage's do - planned, run, installed - before finish()
@@ -1886,10 +1506,8 @@ extern "C" int cto_realign_windows(int n_jobs, cto_realign_job* jobs, int where,
     // A window owns thousands of small vectors (a hit per read and haplotype) and giving ~100 k of them back costs as much as the
     // traceback stage (and more when many threads free into each other's arenas): the windows are handed to a thread that does it
     // behind the caller's back; the next call (or the library's unloading) waits for it.
-    static const bool inline_teardown = std::getenv("CTO_REALIGN_INLINE_TEARDOWN") != nullptr;      // A/B switch
-    if (inline_teardown) parallel_for(ws.size(), threads, [&](size_t i) { ws[i] = Window(); });
     if (stats) stats->host_ms = now_ms() - t1;
-    if (!inline_teardown) reap(std::move(ws));
+    reap(std::move(ws));
     if (first_bad >= 0) { cto::set_error("window %d: %s", first_bad, errors[size_t(first_bad)].c_str()); return status[size_t(first_bad)]; }
     return CTO_OK;
 }
