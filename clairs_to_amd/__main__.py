@@ -1,11 +1,12 @@
 """`python -m clairs_to_amd <submodule> ...` - same dispatch style as the reference's clairs_to.py:84-107 for the
-hot-path sub-modules this package replaces; each takes the argv run_clairs_to builds for its namesake (tests/test_cli_argv.py)."""
+hot-path sub-modules this package replaces and the post-calling steps it mirrors (the short-read chain is complete: realign_variants ->
+postfilter_variants -> postprocess_vcf); each takes the argv run_clairs_to builds for its namesake (tests/test_cli_argv.py)."""
 import importlib
 import sys
 
 SUBMODULES = ("extract_candidates_calling", "concat_files", "create_tensor_pileup_calling", "predict", "call_variants", "pileup_call", "call_chunks",
               "sort_vcf", "postprocess_vcf", "haplotype_filtering", "realign_reads", "realign_variants",
-              "nonsomatic_tagging")
+              "nonsomatic_tagging", "postfilter_variants")
 
 
 def dispatch(name, argv):

@@ -75,6 +75,11 @@ class PonStats(C.Structure):
                 ("used_tbi", c_i32), ("kind", c_i32), ("seconds", C.c_double)]
 
 
+class PfView(C.Structure):
+    _fields_ = [("n_cols", c_i64), ("n_names", c_i64), ("n_keys", c_i64), ("n_tokens", c_i64), ("col_pos", c_vp), ("col_off", c_vp),
+                ("ent_tok", c_vp), ("ent_rid", c_vp), ("col_tok_off", c_vp), ("tok_cnt", c_vp), ("tok_meta", c_vp), ("col_flags", c_vp)]
+
+
 class RunStats(C.Structure):
     _fields_ = [("candidates", c_i64), ("sites", c_i64), ("rows", c_i64), ("low_coverage", c_i64), ("clamped", c_i64), ("seconds", C.c_double),
                 ("produce_s", C.c_double), ("finish_s", C.c_double), ("launch_s", C.c_double), ("launcher_wait_s", C.c_double),
@@ -172,6 +177,12 @@ SYMBOLS = {
     "cto_pon_match_file": (C.c_int, [c_vp, C.c_char_p, C.c_char_p, C.c_int, c_vp, C.POINTER(PonStats), c_vp]),
     "cto_pon_host_lines": (c_i64, [c_vp, C.POINTER(c_vp), C.POINTER(c_vp), C.POINTER(c_vp)]),
     "cto_tbi_contig_chunks": (c_i64, [c_vp, C.c_size_t, C.c_char_p, c_vp, c_i64]),
+    "cto_postfilter_pack": (C.c_int, [c_vp, C.c_size_t, C.c_char_p, c_i64, C.c_size_t, C.c_int, C.POINTER(c_vp)]),
+    "cto_postfilter_view_of": (C.c_int, [c_vp, C.POINTER(PfView)]),
+    "cto_postfilter_key_string": (C.c_int, [c_vp, c_i64, C.POINTER(C.c_char_p)]),
+    "cto_postfilter_token_string": (C.c_int, [c_vp, c_i64, c_i64, C.POINTER(C.c_char_p)]),
+    "cto_postfilter_free": (None, [c_vp]),
+    "cto_postfilter_windows": (C.c_int, [C.c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int, c_vp, C.POINTER(C.c_double)]),
     "cto_posterior_from_probs": (C.c_int, [c_vp, C.c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 

@@ -688,6 +688,63 @@ int64_t cto_pon_host_lines(cto_pon* ctx, const char** bytes, const int64_t** off
  * (0: the index does not name the contig), CTO_ENOMEM when `cap` pairs do not hold them, CTO_EINVAL when the bytes are not a tabix index. */
 int64_t cto_tbi_contig_chunks(const uint8_t* tbi_file, size_t len, const char* ctg, uint64_t* chunks, int64_t cap);
 
+/* ------------------------------------------------------------------------------------------------
+ * Short-read post-calling filters on the DEVICE (src/postfilter_variants.py; csrc/postfilter.hip): the read-level
+ * evidence of every call of a batch of mpileup jobs, from the eight-column text of
+ *   samtools mpileup --min-MQ q --min-BQ q --excl-flags 2316 -r ctg:lo-hi --output-MQ --output-QNAME        (:263-270)
+ *
+ * cto_postfilter_pack     one job's text -> a packed job (host; get_base_list :147-179 and _parse_mpileup_postfilter_chunk_dict :239-260
+ *                         restated, quirks included: '^' marks the entry BEFORE it (index -1 = the row's last name at the start of a
+ *                         row), '$' the current one, the larger of the start and the end index set is kept (the end set on a tie),
+ *                         characters outside "ACGTNacgtn#*" make no entry, rows with fewer than 8 fields are skipped, the 8th field is
+ *                         taken as the row holds it (the last name of a row whose 8th field ends the line carries the '\n'), the read
+ *                         key is QNAME + "_1" for a lower-case base or '#', else "_0").  Rows must come in ascending POS.
+ *                         ref_seq = upper-cased reference of [region_lo, region_lo + ref_len); flanking = --flanking.
+ *   view                  col_pos[n_cols], col_off[n_cols + 1] into the per-NAME arrays (a row's names beyond its entries are kept,
+ *                         flagged CTO_PF_EXTRA: the reference counts them in the depth at the call), ent_tok (token index within the
+ *                         column | CTO_PF_* flags), ent_rid (read keys interned per job, first seen first), col_tok_off[n_cols + 1]
+ *                         into the per-column token tables (token = upper(base + indel string), first seen first): tok_cnt (entries of
+ *                         the column with it), tok_meta (bit 0: equals the reference base, bit 1: is "#" or "*", bits 8..: min(len - 1,
+ *                         2 flanking) of an indel string "+..." longer than 3, :308-309), col_flags (bit 0: len(start/end set) >=
+ *                         len(entries) * 0.2 in double, :409).
+ * cto_postfilter_windows  per call (job index, POS, kind 0 SNV / 1 insertion / 2 deletion / 3 neither, len(REF), ALT =
+ *                         alt_bytes[alt_off[i], alt_off[i + 1])) over the window [max(POS - flanking, 1), POS + flanking] (:382-383):
+ *                         out[i][0..9] = |A| (the alt read-key set of :424-434), |A & union of the qualifying columns' start/end
+ *                         names| (:409-411, :293), match_count (:302-341), ins_length (:308-309), depth (:418), a0, r0, a1, r1
+ *                         (:347-350), path (0: evaluated by the kernel, 1: by the host code of this call).  One workgroup per call; A
+ *                         and the union are LDS bitsets over read id - the window's smallest id.  A window whose id range exceeds
+ *                         max_id_range (0: what the bitsets hold, CTO_PF_ID_RANGE) or that has a column of more than 64 distinct tokens
+ *                         is evaluated by the host code, with the same result.  The thresholds of :332-338 are evaluated in double,
+ *                         multiply then compare.  kernel_ms (may be NULL): HIP-event time of the kernel.  The caller turns the integers
+ *                         into the four booleans and Fisher's p (:293, :344, :353).  Thread-safe (the device part is serialised).
+ * ---------------------------------------------------------------------------------------------- */
+#define CTO_PF_SUPERSEDED 0x80000000u   /* the same key occurs again later among the column's entries (dict(zip()) keeps the last) */
+#define CTO_PF_RSE        0x40000000u   /* the name the column's kept start/end index set points at                                */
+#define CTO_PF_ENDS0      0x20000000u   /* key ends in '0' (forward, :419) */
+#define CTO_PF_ENDS1      0x10000000u   /* key ends in '1' (reverse, :421) */
+#define CTO_PF_EXTRA      0x08000000u   /* a name beyond the row's entries: no token                                               */
+#define CTO_PF_TOKEN_MASK 0x000fffffu
+#define CTO_PF_ID_RANGE   8192
+typedef struct cto_pf_view {
+    int64_t n_cols, n_names, n_keys, n_tokens;
+    const int32_t*  col_pos;
+    const int64_t*  col_off;
+    const uint32_t* ent_tok;
+    const uint32_t* ent_rid;
+    const int64_t*  col_tok_off;
+    const uint32_t* tok_cnt;
+    const uint32_t* tok_meta;
+    const uint8_t*  col_flags;
+} cto_pf_view;
+int  cto_postfilter_pack(const char* text, size_t len, const char* ref_seq, int64_t region_lo, size_t ref_len, int flanking, void** job);
+int  cto_postfilter_view_of(const void* job, cto_pf_view* view);
+int  cto_postfilter_key_string(const void* job, int64_t rid, const char** s);                 /* NUL-terminated, owned by the job */
+int  cto_postfilter_token_string(const void* job, int64_t col, int64_t tok, const char** s);
+void cto_postfilter_free(void* job);
+int  cto_postfilter_windows(int n_jobs, void* const* jobs, int64_t n_calls, const int32_t* call_job, const int32_t* call_pos,
+                            const int32_t* call_kind, const int32_t* call_ref_len, const char* alt_bytes, const int64_t* alt_off,
+                            int max_id_range, int64_t* out, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
