@@ -1,12 +1,13 @@
 """`python -m clairs_to_amd <submodule> ...` - same dispatch style as the reference's clairs_to.py:84-107 for the
 hot-path sub-modules this package replaces and the post-calling steps it mirrors (the short-read chain is complete: realign_variants ->
-postfilter_variants -> postprocess_vcf); each takes the argv run_clairs_to builds for its namesake (tests/test_cli_argv.py)."""
+postfilter_variants -> postprocess_vcf); each takes the argv run_clairs_to builds for its namesake (tests/test_cli_argv.py).
+allele_counter takes alleleCounter's own options (the first command of the Verdict step, src/cna_germline_tagging.py:56-71)."""
 import importlib
 import sys
 
 SUBMODULES = ("extract_candidates_calling", "concat_files", "create_tensor_pileup_calling", "predict", "call_variants", "pileup_call", "call_chunks",
               "sort_vcf", "postprocess_vcf", "haplotype_filtering", "realign_reads", "realign_variants",
-              "nonsomatic_tagging", "postfilter_variants")
+              "nonsomatic_tagging", "postfilter_variants", "allele_counter")
 
 
 def dispatch(name, argv):

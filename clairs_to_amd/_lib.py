@@ -80,6 +80,11 @@ class PfView(C.Structure):
                 ("ent_tok", c_vp), ("ent_rid", c_vp), ("col_tok_off", c_vp), ("tok_cnt", c_vp), ("tok_meta", c_vp), ("col_flags", c_vp)]
 
 
+class AlleleStats(C.Structure):
+    _fields_ = [("n_chunks", c_i64), ("n_reads_entered", c_i64), ("n_blocks", c_i64), ("inflated_bytes", c_i64), ("fallback_chunks", c_i64),
+                ("ms_inflate", C.c_double), ("ms_records", C.c_double), ("ms_count", C.c_double)]
+
+
 class RunStats(C.Structure):
     _fields_ = [("candidates", c_i64), ("sites", c_i64), ("rows", c_i64), ("low_coverage", c_i64), ("clamped", c_i64), ("seconds", C.c_double),
                 ("produce_s", C.c_double), ("finish_s", C.c_double), ("launch_s", C.c_double), ("launcher_wait_s", C.c_double),
@@ -184,6 +189,8 @@ SYMBOLS = {
     "cto_postfilter_free": (None, [c_vp]),
     "cto_postfilter_windows": (C.c_int, [C.c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int, c_vp, C.POINTER(C.c_double)]),
     "cto_posterior_from_probs": (C.c_int, [c_vp, C.c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "cto_allele_counts": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, c_vp, c_i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_vp,
+                                    c_vp, C.POINTER(AlleleStats)]),
 }
 
 for _name, (_res, _args) in SYMBOLS.items():

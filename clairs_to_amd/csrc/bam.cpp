@@ -49,6 +49,7 @@
 #include <deque>
 #include <memory>
 #include <thread>
+#include <unordered_map>
 
 #include "pack_internal.h"
 
@@ -861,6 +862,174 @@ extern "C" int cto_pack_from_bam_inflated(const char* bam_path, const char* bai_
                                   max_depth, max_indel_length, pre, out);
     });
 }
+
+// ------------------------------------------------------------------------------------------------ allele counter, host path
+// The plain definition of the allele-count rules (listed in full at the top of csrc/allelecount.hip, which holds the C entry point and
+// the device path that is held equal to this one).  One call = one run of loci on one thread: every read that overlaps
+// ctg:loci[0]-loci[n-1] is read through the index, filtered, kept; a second pass in file order walks each read's CIGAR along the loci
+// it covers.  Only names that occur more than once among the entered reads need the per-locus memory of "the first read of this name".
+namespace cto {
+
+int allele_counts_host_range(const char* bam_path, const char* bai_path, const char* ctg_name, const int32_t* loci, int64_t n_loci,
+                             const AlleleParams& pr, int32_t* counts, int64_t* n_entered, double* ms_records, double* ms_count) {
+    auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double t0 = now();
+    memset(counts, 0, size_t(n_loci) * 4 * sizeof(int32_t));
+    Bgzf bz;
+    CTO_REQUIRE(bz.open(bam_path), CTO_EINVAL, "cto_allele_counts: %s", bz.err.c_str());
+    int tid = -1;
+    {
+        const int rch = read_header_tid(bz, bam_path, ctg_name, &tid);
+        if (rch != CTO_OK) return rch;
+    }
+    const int64_t beg0 = int64_t(loci[0]) - 1, end0 = loci[n_loci - 1];
+    std::vector<Chunk> chunks;
+    {
+        std::string err, idx = bai_path ? std::string(bai_path) : std::string(bam_path) + ".bai";
+        CTO_REQUIRE(bai_query(idx.c_str(), tid, beg0, end0, &chunks, &err), CTO_EINVAL, "cto_allele_counts: %s", err.c_str());
+    }
+    struct ARead {
+        int32_t pos, end, l_seq;
+        int name_id;
+        size_t seq_off, qual_off;
+        std::vector<uint32_t> cigar;
+        std::vector<uint8_t> raw;
+    };
+    std::vector<ARead> reads;
+    std::unordered_map<std::string, int> name_ids;
+    std::vector<int> name_uses;
+    std::vector<uint8_t> rec;
+    uint8_t h4[4];
+    bool done = false;
+    for (size_t ci = 0; ci < chunks.size() && !done; ++ci) {
+        CTO_REQUIRE(bz.seek(chunks[ci].beg), CTO_EINVAL, "cto_allele_counts: seek into BAM failed: %s", bz.err.c_str());
+        while (bz.tell() < chunks[ci].end) {
+            if (!bz.read(h4, 4)) { CTO_REQUIRE(bz.err.empty(), CTO_EINVAL, "cto_allele_counts: %s", bz.err.c_str()); done = true; break; }
+            const int bsz = le32(h4);
+            CTO_REQUIRE(bsz >= 32 && bsz <= (1 << 28), CTO_EINVAL, "cto_allele_counts: bad alignment block size %d", bsz);
+            rec.resize(size_t(bsz));
+            CTO_REQUIRE(bz.read(rec.data(), rec.size()), CTO_EINVAL, "cto_allele_counts: truncated alignment record%s%s", bz.err.empty() ? "" : ": ", bz.err.c_str());
+            const uint8_t* b = rec.data();
+            const int rtid = le32(b), pos = le32(b + 4);
+            const int l_name = b[8], mapq = b[9];
+            const int n_cig = b[12] | (b[13] << 8), flag = b[14] | (b[15] << 8);
+            const int l_seq = le32(b + 16);
+            if (rtid != tid) { if (rtid > tid || rtid < 0) { done = true; break; } continue; }
+            if (pos >= end0) { done = true; break; }
+            if (mapq < pr.min_mq || (flag & pr.excl_flags) || (flag & pr.req_flags) != pr.req_flags) continue;
+            if ((pr.req_flags & 2) && (((flag & 32) != 0) == ((flag & 16) != 0))) continue;     // proper pairs must be F/R
+            if ((flag & 1796) || n_cig == 0 || l_seq <= 0 || pos < 0) continue;                 // the pile-up iterator's own mask
+            const size_t need = 32 + size_t(l_name) + size_t(n_cig) * 4 + size_t((l_seq + 1) / 2) + size_t(l_seq);
+            CTO_REQUIRE(need <= rec.size(), CTO_EINVAL, "cto_allele_counts: alignment record shorter than its fields");
+            const uint8_t* cg = b + 32 + l_name;
+            const uint8_t* sq = cg + size_t(n_cig) * 4;
+            const uint8_t* ql = sq + (l_seq + 1) / 2;
+            int n_ops = n_cig;
+            const uint8_t* ops = cg;
+            resolve_cg_tag(cg, n_cig, l_seq, ql + l_seq, rec.data() + rec.size(), &ops, &n_ops);
+            ARead r;
+            r.cigar.resize(size_t(n_ops));
+            int64_t rlen = 0, qlen = 0;
+            for (int i = 0; i < n_ops; ++i) {
+                const uint32_t c = uint32_t(le32(ops + i * 4));
+                r.cigar[size_t(i)] = c;
+                const int opc = int(c & 15), len = int(c >> 4);
+                if (opc == 0 || opc == 2 || opc == 3 || opc == 7 || opc == 8) rlen += len;
+                if (opc == 0 || opc == 1 || opc == 4 || opc == 7 || opc == 8) qlen += len;
+            }
+            if (qlen != l_seq || rlen == 0) continue;
+            CTO_REQUIRE(int64_t(pos) + rlen <= INT32_MAX, CTO_EINVAL, "cto_allele_counts: alignment at %d runs past 2^31 - 1", pos);
+            if (int64_t(pos) + rlen <= beg0) continue;
+            r.pos = pos;
+            r.end = int32_t(pos + rlen);
+            r.l_seq = l_seq;
+            r.seq_off = size_t(sq - b);
+            r.qual_off = size_t(ql - b);
+            const auto it = name_ids.emplace(std::string(reinterpret_cast<const char*>(b + 32), size_t(std::max(0, l_name - 1))), int(name_uses.size()));
+            if (it.second) name_uses.push_back(0);
+            r.name_id = it.first->second;
+            ++name_uses[size_t(r.name_id)];
+            r.raw.swap(rec);
+            reads.push_back(std::move(r));
+        }
+    }
+    const double t1 = now();
+    // (locus index, name) -> base code of the first read of that name that covers the locus
+    std::unordered_map<uint64_t, uint8_t> first_c;
+    for (const ARead& r : reads) {
+        const bool shared_name = name_uses[size_t(r.name_id)] > 1;
+        int64_t li = std::lower_bound(loci, loci + n_loci, r.pos + 1) - loci;          // loci are 1-based
+        int32_t rp = r.pos, qp = 0;
+        for (size_t k = 0; k < r.cigar.size() && li < n_loci && loci[li] <= r.end; ++k) {
+            const int len = int(r.cigar[k] >> 4), opc = int(r.cigar[k] & 15);
+            const bool cons_ref = opc == 0 || opc == 2 || opc == 3 || opc == 7 || opc == 8;
+            const bool cons_q = opc == 0 || opc == 1 || opc == 4 || opc == 7 || opc == 8;
+            if (cons_ref) {
+                const bool is_del = opc == 2 || opc == 3;
+                for (; li < n_loci && int64_t(loci[li]) - 1 < int64_t(rp) + len; ++li) {
+                    const int q = is_del ? qp : qp + (loci[li] - 1 - rp);
+                    const int c = q < r.l_seq ? (r.raw[r.seq_off + size_t(q >> 1)] >> ((~q & 1) << 2)) & 15 : 0;
+                    const int bq = q < r.l_seq ? int(r.raw[r.qual_off + size_t(q)]) : 0;
+                    bool counts_here = !is_del && bq >= pr.min_bq;
+                    if (shared_name) {
+                        const auto ins = first_c.emplace((uint64_t(li) << 32) | uint32_t(r.name_id), uint8_t(c));
+                        if (!ins.second && int(ins.first->second) == c) counts_here = false;
+                    }
+                    if (counts_here) {
+                        const int slot = c == 1 ? 0 : (c == 2 ? 1 : (c == 4 ? 2 : (c == 8 ? 3 : -1)));
+                        if (slot >= 0) ++counts[li * 4 + slot];
+                    }
+                }
+                rp += len;
+            }
+            if (cons_q) qp += len;
+        }
+    }
+    if (n_entered) *n_entered = int64_t(reads.size());
+    if (ms_records) *ms_records = t1 - t0;
+    if (ms_count) *ms_count = now() - t1;
+    return CTO_OK;
+}
+
+// Cuts a contig's loci into chunks whose inflated alignment bytes are expected to stay within `budget`: the linear index names, per
+// 16 kb window, the file offset of the first alignment that overlaps it, so the compressed bytes between two positions are read off it
+// (interpolated inside a window) and taken times four, the usual ratio of a BAM.  cuts = chunk boundaries as loci indices, 0 .. n_loci.
+int allele_plan_chunks(const char* bam_path, const char* bai_path, const char* ctg_name, const int32_t* loci, int64_t n_loci, int64_t budget,
+                       std::vector<int64_t>* cuts) {
+    cuts->assign(1, 0);
+    Bgzf bz;
+    CTO_REQUIRE(bz.open(bam_path), CTO_EINVAL, "cto_allele_counts: %s", bz.err.c_str());
+    int tid = -1;
+    const int rch = read_header_tid(bz, bam_path, ctg_name, &tid);
+    if (rch != CTO_OK) return rch;
+    std::vector<Chunk> chunks;
+    std::vector<uint64_t> linear;
+    std::string err, idx = bai_path ? std::string(bai_path) : std::string(bam_path) + ".bai";
+    CTO_REQUIRE(bai_query(idx.c_str(), tid, int64_t(loci[0]) - 1, loci[n_loci - 1], &chunks, &err, &linear), CTO_EINVAL, "cto_allele_counts: %s", err.c_str());
+    if (chunks.empty() || linear.empty()) { cuts->push_back(n_loci); return CTO_OK; }
+    int64_t file_lo = int64_t(chunks.front().beg >> 16), file_hi = 0;
+    for (const Chunk& c : chunks) file_hi = std::max<int64_t>(file_hi, int64_t(c.end >> 16) + 65536);
+    std::vector<int64_t> woff(linear.size() + 1);
+    for (size_t w = 0; w < linear.size(); ++w) {
+        int64_t v = int64_t(linear[w] >> 16);
+        if (v == 0) v = w ? woff[w - 1] : file_lo;                  // a window without alignments
+        v = std::min(std::max(v, file_lo), file_hi);
+        woff[w] = w ? std::max(v, woff[w - 1]) : v;
+    }
+    woff[linear.size()] = file_hi;
+    auto at = [&](int64_t p0) -> double {
+        const int64_t w = p0 >> 14;
+        if (w >= int64_t(linear.size())) return double(file_hi);
+        return double(woff[size_t(w)]) + double(woff[size_t(w) + 1] - woff[size_t(w)]) * double(p0 & 16383) / 16384.0;
+    };
+    int64_t s = 0;
+    for (int64_t i = 1; i < n_loci; ++i)
+        if (4.0 * (at(loci[i]) - at(loci[s] - 1)) > double(budget)) { cuts->push_back(i); s = i; }
+    cuts->push_back(n_loci);
+    return CTO_OK;
+}
+
+}  // namespace cto
 
 // The byte range of the BAM that holds every BGZF block the index names for ctg:start-end (the block the last chunk ends in
 // included: a BGZF block is at most 64 KiB long).

@@ -35,6 +35,7 @@
 #include <memory>
 #include <string>
 #include <vector>
+#include "bam_records.h"
 #include "common.h"
 #include "hip_buffers.h"
 #include "pack_internal.h"
@@ -44,182 +45,8 @@ using namespace cto;
 
 namespace {
 
-struct DevRead {
-    uint32_t off;                 // of the record (its block_size field) in the linear stream
-    int32_t pos, end;             // 0-based, end exclusive
-    uint32_t ops_off;             // CIGAR operations (the field or the CG tag)
-    int32_t n_ops;
-    uint32_t seq_off, qual_off;
-    int32_t l_seq;
-    uint8_t mapq, rev, no_qual, valid;
-};
-
 struct TmpEnt { uint32_t entry, rank, ind_q, ind; };      // ind = len << 2 | kind (0 none, 1 ins, 2 del)
 struct KeyRec { uint32_t read, q, len; uint8_t code, kind, overlong, group; };
-
-struct Flags {                    // written by the kernels, read by the host after each phase
-    int stop_idx, err_idx, paired_idx, skip_idx;    // first record index with the condition (INT_MAX: none)
-    int bad_chain, deep_col, many_keys, ref_oob;
-    int bad_crc;                                    // 1 + index of a block whose inflated bytes fail the gzip trailer's CRC-32 (0: none)
-    int n_rec, n_valid, n_cols, n_keys;
-    long long n_entries, key_str_bytes;
-    int max_live, max_len;                          // largest number of accepted reads still open at another accepted read's start;
-                                                    // longest reference span of an accepted read
-};
-
-__device__ __forceinline__ uint32_t ld16(const uint8_t* p) { return uint32_t(p[0]) | (uint32_t(p[1]) << 8); }
-__device__ __forceinline__ uint32_t ld32(const uint8_t* p) { return uint32_t(p[0]) | (uint32_t(p[1]) << 8) | (uint32_t(p[2]) << 16) | (uint32_t(p[3]) << 24); }
-
-__global__ void k_linearise(const uint8_t* __restrict__ src, const cto_bgzf_block* __restrict__ blocks, const int64_t* __restrict__ lin_off,
-                            uint8_t* __restrict__ lin) {
-    const cto_bgzf_block b = blocks[blockIdx.x];
-    const uint8_t* s = src + b.out_off;
-    uint8_t* d = lin + lin_off[blockIdx.x];
-    for (uint32_t i = threadIdx.x; i < b.isize; i += blockDim.x) d[i] = s[i];
-}
-
-// CRC-32 of every inflated block against its gzip trailer, as htslib (and the host reader) checks it: one wave per block, lane k
-// runs the byte-table CRC over its own slice (the first slice is the short one, every other one 1024 bytes), lane 0 then chains the
-// 64 partial registers: state after slice k = P_k xor Z(state after slice k-1), Z = "1024 zero bytes" as a 32 x 32 bit matrix
-// (z1k[i] = image of bit i, from the host) - a CRC register is linear in its start value.
-__global__ __launch_bounds__(64) void k_crc32_blocks(const uint8_t* __restrict__ src, const cto_bgzf_block* __restrict__ blocks, int n_blocks,
-                                                     const uint32_t* __restrict__ z1k, Flags* fl) {
-    __shared__ uint32_t table[256];
-    __shared__ uint32_t part[64];
-    __shared__ uint32_t zm[32];
-    const int lane = threadIdx.x;
-    for (int i = lane; i < 256; i += 64) {
-        uint32_t c = uint32_t(i);
-        for (int k = 0; k < 8; ++k) c = (c & 1u) ? 0xEDB88320u ^ (c >> 1) : c >> 1;
-        table[i] = c;
-    }
-    if (lane < 32) zm[lane] = z1k[lane];
-    __syncthreads();
-    for (int b = blockIdx.x; b < n_blocks; b += gridDim.x) {
-        const cto_bgzf_block bd = blocks[b];
-        const int n = int(bd.isize);
-        if (n == 0) continue;
-        const int ns = (n + 1023) / 1024, r = n - 1024 * (ns - 1);
-        const uint8_t* p = src + bd.out_off;
-        uint32_t c = lane == 0 ? 0xFFFFFFFFu : 0u;
-        if (lane < ns) {
-            const int lo = lane == 0 ? 0 : r + 1024 * (lane - 1), len = lane == 0 ? r : 1024;
-            for (int i = 0; i < len; ++i) c = table[(c ^ p[lo + i]) & 0xFFu] ^ (c >> 8);
-        }
-        __syncthreads();
-        part[lane] = c;
-        __syncthreads();
-        if (lane == 0) {
-            uint32_t st = part[0];
-            for (int k = 1; k < ns; ++k) {
-                uint32_t z = 0;
-                for (int i = 0; i < 32; ++i) z ^= ((st >> i) & 1u) ? zm[i] : 0u;
-                st = part[k] ^ z;
-            }
-            if ((st ^ 0xFFFFFFFFu) != bd.crc32) atomicCAS(&fl->bad_crc, 0, b + 1);
-        }
-    }
-}
-
-// chain k walks the records from starts[k] to starts[k + 1]; mode 0 counts, mode 1 writes their offsets at base[k]..
-__global__ void k_chain(const uint8_t* __restrict__ lin, int64_t len, const int64_t* __restrict__ starts, int n_chains, int mode,
-                        int* __restrict__ counts, const int* __restrict__ base, uint32_t* __restrict__ rec_off, Flags* fl) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n_chains) return;
-    int64_t o = starts[k];
-    const int64_t limit = starts[k + 1];
-    int n = 0;
-    while (o < limit && o + 4 <= len) {
-        const int64_t bsz = int64_t(int32_t(ld32(lin + o)));
-        if (bsz < 32) { atomicExch(&fl->bad_chain, 2); break; }
-        if (o + 4 + bsz > len) break;                         // the span ends inside a record the region does not need
-        if (mode) rec_off[base[k] + n] = uint32_t(o);
-        ++n;
-        o += 4 + bsz;
-    }
-    if (o > limit) atomicExch(&fl->bad_chain, 1);              // a named offset that is not a record boundary
-    if (!mode) counts[k] = n;
-}
-
-__global__ void k_parse(const uint8_t* __restrict__ lin, const uint32_t* __restrict__ rec_off, int n_rec, int tid, int beg0, int end0,
-                        int excl_flags, int min_mq, DevRead* __restrict__ reads, Flags* fl) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_rec) return;
-    DevRead r{};
-    r.off = rec_off[i];
-    const uint8_t* b = lin + r.off + 4;
-    const int64_t bsz = int64_t(int32_t(ld32(lin + r.off)));
-    const int rtid = int(ld32(b)), pos = int(ld32(b + 4));
-    const int l_name = b[8], mapq = b[9];
-    const int n_cig = int(ld16(b + 12)), flag = int(ld16(b + 14));
-    const int l_seq = int(ld32(b + 16));
-    bool stop = false, ok = false;
-    if (rtid != tid) stop = rtid > tid || rtid < 0;
-    else if (pos >= end0) stop = true;
-    else if (!((flag & excl_flags) || (flag & 4) || mapq < min_mq || n_cig == 0 || l_seq <= 0 || pos < 0 || ((flag & 1) && !(flag & 2)))) ok = true;
-    if (stop) atomicMin(&fl->stop_idx, i);
-    if (ok) {
-        const int64_t need = 32 + int64_t(l_name) + int64_t(n_cig) * 4 + int64_t((l_seq + 1) / 2) + int64_t(l_seq);
-        if (need > bsz) { atomicMin(&fl->err_idx, i); ok = false; }
-    }
-    if (ok) {
-        const uint8_t* cg = b + 32 + l_name;
-        const uint8_t* sq = cg + size_t(n_cig) * 4;
-        const uint8_t* ql = sq + (l_seq + 1) / 2;
-        int n_ops = n_cig;
-        const uint8_t* ops = cg;
-        if (n_cig == 2 && (ld32(cg) & 15) == 4 && int(ld32(cg) >> 4) == l_seq && (ld32(cg + 4) & 15) == 3) {     // CG:B,I holds the real CIGAR
-            const uint8_t* aux = ql + l_seq;
-            const uint8_t* aend = b + bsz;
-            while (aux + 3 <= aend) {
-                const char t0 = char(aux[0]), t1 = char(aux[1]), ty = char(aux[2]);
-                aux += 3;
-                size_t skip = 0;
-                if (ty == 'A' || ty == 'c' || ty == 'C') skip = 1;
-                else if (ty == 's' || ty == 'S') skip = 2;
-                else if (ty == 'i' || ty == 'I' || ty == 'f') skip = 4;
-                else if (ty == 'Z' || ty == 'H') { while (aux + skip < aend && aux[skip]) ++skip; ++skip; }
-                else if (ty == 'B') {
-                    if (aux + 5 > aend) break;
-                    const char sub = char(aux[0]);
-                    const uint32_t cnt = ld32(aux + 1);
-                    const size_t esz = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : 4;
-                    if (t0 == 'C' && t1 == 'G' && sub == 'I' && aux + 5 + size_t(cnt) * 4 <= aend) { n_ops = int(cnt); ops = aux + 5; break; }
-                    skip = 5 + size_t(cnt) * esz;
-                } else break;
-                aux += skip;
-            }
-        }
-        long long rlen = 0, qlen = 0;
-        bool has_skip = false;
-        for (int k = 0; k < n_ops; ++k) {
-            const uint32_t c = ld32(ops + size_t(k) * 4);
-            const int opc = int(c & 15), len = int(c >> 4);
-            if (opc == 0 || opc == 2 || opc == 3 || opc == 7 || opc == 8) rlen += len;
-            if (opc == 0 || opc == 1 || opc == 4 || opc == 7 || opc == 8) qlen += len;
-            has_skip |= opc == 3;
-        }
-        if (qlen != l_seq || rlen == 0) ok = false;
-        else if (int64_t(pos) + rlen > 0x7fffffffLL) { atomicMin(&fl->err_idx, i); ok = false; }
-        else if (pos + rlen <= beg0) ok = false;
-        if (ok) {
-            r.pos = pos;
-            r.end = int32_t(pos + rlen);
-            r.ops_off = uint32_t(ops - lin);
-            r.n_ops = n_ops;
-            r.seq_off = uint32_t(sq - lin);
-            r.qual_off = uint32_t(ql - lin);
-            r.l_seq = l_seq;
-            r.mapq = uint8_t(mapq);
-            r.rev = (flag & 16) != 0;
-            r.no_qual = ql[0] == 0xff;
-            r.valid = 1;
-            if (flag & 1) atomicMin(&fl->paired_idx, i);
-            if (has_skip) atomicMin(&fl->skip_idx, i);
-        }
-    }
-    reads[i] = r;
-}
 
 // accepted reads (in front of the record that ended the scan) in file order: rid[j] = record index
 __global__ void k_compact(const DevRead* __restrict__ reads, int n_rec, int* __restrict__ rid, Flags* fl) {
@@ -843,9 +670,8 @@ extern "C" int cto_pileup_device(cto_dev_pileup* cx, const void* d_inflated, con
     CTO_HIP(hipMemsetAsync(cx->diff.p, 0, size_t(total + 1) * 4, s));
     const uint8_t* lin = cx->lin.as<uint8_t>();
     if (!cx->z1k_ready) {                                     // "1024 zero bytes" as a bit matrix, once per context
-        uint32_t tbl[256], z[32];
-        for (uint32_t i = 0; i < 256; ++i) { uint32_t c = i; for (int k = 0; k < 8; ++k) c = (c & 1u) ? 0xEDB88320u ^ (c >> 1) : c >> 1; tbl[i] = c; }
-        for (int i = 0; i < 32; ++i) { uint32_t c = 1u << i; for (int k = 0; k < 1024; ++k) c = tbl[c & 0xFFu] ^ (c >> 8); z[i] = c; }
+        uint32_t z[32];
+        crc32_zero_1k_matrix(z);
         if ((rc = cx->z1k.ensure(sizeof(z)))) return rc;
         CTO_HIP(hipMemcpy(cx->z1k.p, z, sizeof(z), hipMemcpyHostToDevice));
         cx->z1k_ready = true;

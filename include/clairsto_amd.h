@@ -745,6 +745,33 @@ int  cto_postfilter_windows(int n_jobs, void* const* jobs, int64_t n_calls, cons
                             const int32_t* call_kind, const int32_t* call_ref_len, const char* alt_bytes, const int64_t* alt_off,
                             int max_id_range, int64_t* out, double* kernel_ms);
 
+/* ----------------------------------------------------------------------------------------------
+ * Allele counter (csrc/allelecount.hip, host rules in csrc/bam.cpp): the per-locus A / C / G / T counts that
+ * `alleleCounter -b BAM -l LOCI -m min_bq -q min_mq -f req_flags -F excl_flags [--dense-snps]` writes for one contig - the first
+ * command of the reference's Verdict step (src/cna_germline_tagging.py:56-71).  PARITY UNPINNED against alleleCounter (no htslib on
+ * the build or GPU machines; tools/pin_allelecounter.sh pins it where the program exists).  The rules are listed at the top of
+ * csrc/allelecount.hip.
+ *   loci        1-based positions on ctg_name, strictly ascending (the caller sorts and removes repeats)
+ *   where       0: host (the plain definition of the rules, `host_threads` threads over chunks of loci; 0 = one per core, at most 32);
+ *               1: device - per chunk of loci: cto_bam_chunk_span, cto_bgzf_scan, copy up, cto_bgzf_inflate, CRC-32, record chain,
+ *               parse, name links, count, all on `stream`.  A chunk whose input is damaged (a block that does not inflate or fails its
+ *               CRC-32, a broken record chain, a record shorter than its fields) is redone by the host path (fallback_chunks), which
+ *               reports the damage if it meets it too.  Paired reads, reference skips, any depth and CG-tag CIGARs stay on the device.
+ *   counts      n_loci x 4 int32 on the host (A, C, G, T)
+ *   stats       may be NULL.  n_reads_entered counts a read once per chunk it overlaps; n_blocks / inflated_bytes / ms_inflate are the
+ *               device path's (HIP-event times: copy up + inflate | CRC .. name links | count + copy down); the host path reports
+ *               the time spent reading records (ms_records) and counting (ms_count), summed over its threads.
+ * CTO_ALLELE_CHUNK_BYTES (environment, for tests): the budget of inflated bytes per chunk; default 256 MiB on the device, 2 MiB on the
+ * host (enough chunks for its threads).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct cto_allele_stats { int64_t n_chunks, n_reads_entered, n_blocks, inflated_bytes, fallback_chunks;
+                                  double ms_inflate, ms_records, ms_count; } cto_allele_stats;
+int cto_allele_counts(const char* bam_path, const char* bai_path, const char* ctg_name,
+                      const int32_t* loci /* 1-based, strictly ascending */, int64_t n_loci,
+                      int min_bq, int min_mq, int req_flags, int excl_flags,
+                      int where /* 0 host, 1 device */, int host_threads, void* stream,
+                      int32_t* counts /* n_loci x 4, host */, cto_allele_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif
