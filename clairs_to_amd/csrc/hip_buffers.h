@@ -1,5 +1,5 @@
 // Host-side plumbing of the device front end (pipeline.hip, pileup.hip, tokenise.hip): buffers that only grow, on the device and
-// page-locked on the host, and waits for the device that sleep instead of spinning.
+// page-locked on the host, waits for the device that sleep instead of spinning, and events and streams that go with their scope.
 #pragma once
 #include <unistd.h>
 #include <cstring>
@@ -64,5 +64,29 @@ inline hipError_t record_and_wait(hipEvent_t ev, hipStream_t s) {
     const hipError_t e = hipEventRecord(ev, s);
     return e != hipSuccess ? e : wait_event(ev);
 }
+
+// An event that goes with its scope
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    int create(unsigned flags = hipEventDefault) { CTO_HIP(hipEventCreateWithFlags(&e, flags)); return CTO_OK; }
+    operator hipEvent_t() const { return e; }
+};
+
+// A stream that goes with its scope: what is queued on it is waited for, then it is destroyed.  Whoever queues on it from another
+// thread must be joined before that - declare the stream BEFORE what joins the threads.
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(const Stream&) = delete;
+    Stream& operator=(const Stream&) = delete;
+    ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
+    int create(unsigned flags = hipStreamNonBlocking) { CTO_HIP(hipStreamCreateWithFlags(&s, flags)); return CTO_OK; }
+    int create_on_cus(const uint32_t* mask, uint32_t words) { CTO_HIP(hipExtStreamCreateWithCUMask(&s, words, mask)); return CTO_OK; }
+    operator hipStream_t() const { return s; }
+};
 
 }  // namespace cto

@@ -13,20 +13,15 @@
 // staging buffers the tokeniser merges into, buffers and contexts kept from chunk to chunk and from call to call, waits that sleep
 // instead of spinning, CU-masked streams for the device inflate (DESIGN.md section 6 has the sequence of measurements).
 // Outputs are byte-identical (tests/test_gpu_cli.py).
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <fcntl.h>
+//
+// Here: the two layouts every stage shares (PackLayout, ResultLayout), a chunk's Slot, Run - the state of one call with the producers'
+// half (produce), the launcher's (launch / launch_stream) and the writers' (finish) - and run_chunks, which sets a call up.  What needs
+// no GPU (files, .fai, BED intervals, the child process, the queue, the clocks) is run_files.h; owning handles are hip_buffers.h.
 #include <unistd.h>
-#include <spawn.h>
-#include <sys/wait.h>
-#include <zlib.h>
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
-#include <condition_variable>
 #include <cstring>
-#include <deque>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -37,19 +32,40 @@
 #include "common.h"
 #include "hip_buffers.h"
 #include "pack_internal.h"
+#include "run_files.h"
 
 using namespace cto;
-
-extern char** environ;
+using namespace cto::run_files;
 
 namespace {
 
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-double cpu_s() { timespec ts; clock_gettime(CLOCK_THREAD_CPUTIME_ID, &ts); return double(ts.tv_sec) + double(ts.tv_nsec) * 1e-9; }   // this thread's CPU time
+// What the writers need of a chunk, in ONE device buffer that comes back with ONE copy:
+// site_info | candidate column vectors | sitefirst | decision | qual | keycnt | keyfirst, each part 256-byte aligned.
+struct ResultLayout {
+    static constexpr size_t SITE_INFO_ROW = 48, COLVEC_ROW = CTO_COLVEC_STRIDE * 2, SITEFIRST_ROW = 32, DECISION_ROW = 16, QUAL_ROW = 8,   // per site
+                            KEYCNT_ROW = 4, KEYFIRST_ROW = 8;                                                                               // per key
+    enum { SITE_INFO, COLVEC, SITEFIRST, DECISION, QUAL, KEYCNT, KEYFIRST, PARTS };
+    size_t off[PARTS] = {0, 0, 0, 0, 0, 0, 0}, total = 0;
+    ResultLayout() = default;
+    ResultLayout(int64_t n_sites, int64_t n_keys) {
+        const size_t n = size_t(n_sites), nk = size_t(std::max<int64_t>(n_keys, 1));
+        const size_t bytes[PARTS] = {n * SITE_INFO_ROW, n * COLVEC_ROW, n * SITEFIRST_ROW, n * DECISION_ROW, n * QUAL_ROW, nk * KEYCNT_ROW, nk * KEYFIRST_ROW};
+        for (int i = 0; i < PARTS; ++i) { off[i] = total; total += (bytes[i] + 255) / 256 * 256; }
+    }
+    // the parts behind `base`: the slot's device buffer or its page-locked copy
+    template <class T> T* part(void* base, int i) const { return reinterpret_cast<T*>(static_cast<char*>(base) + off[i]); }
+    int32_t* site_info(void* base) const { return part<int32_t>(base, SITE_INFO); }
+    int16_t* colvec(void* base) const { return part<int16_t>(base, COLVEC); }
+    int32_t* sitefirst(void* base) const { return part<int32_t>(base, SITEFIRST); }
+    int32_t* decision(void* base) const { return part<int32_t>(base, DECISION); }
+    double* qual(void* base) const { return part<double>(base, QUAL); }
+    uint32_t* keycnt(void* base) const { return part<uint32_t>(base, KEYCNT); }
+    int32_t* keyfirst(void* base) const { return part<int32_t>(base, KEYFIRST); }
+};
 
 struct Slot {
     // pack on the device
-    DevBuf pack_dev;                     // the pack arrays + the candidate positions, one allocation (256-byte aligned parts)
+    DevBuf pack_dev;                     // the pack arrays + the candidate positions, one allocation (PackLayout)
     PinBuf stage;                        // its page-locked source
     const int32_t* d_site_pos = nullptr;
     // featurisation / network / epilogue outputs
@@ -59,11 +75,10 @@ struct Slot {
     PinBuf cand_host;
     DevBuf xmode;                        // REGION jobs with a confident BED / an indel BED / a hybrid list: intervals, positions, hybrid_info records
     PinBuf xmode_host;
-    DevBuf res_dev;                      // site_info | candidate column vectors | sitefirst | decision | qual | keycnt | keyfirst
+    DevBuf res_dev;                      // the chunk's results (ResultLayout)
     PinBuf res_host;                     // the same bytes on the host, one copy per chunk
-    size_t roff[7] = {0, 0, 0, 0, 0, 0, 0};
-    hipEvent_t uploaded = nullptr, begin = nullptr, computed = nullptr, done = nullptr, kernels_end = nullptr;
-    size_t res_total = 0;
+    ResultLayout res;                    // of the chunk in the slot, set when it is launched
+    Event uploaded, begin, computed, done, kernels_end;
     // host side of the chunk
     int64_t job = -1;
     int device = 0;
@@ -73,15 +88,16 @@ struct Slot {
     std::string ref;
     int64_t ref_start = 0;
     cto_dev_tokeniser* tok = nullptr;    // text input with cfg.device_tokenise: the slot's tokeniser context (text staging + row tables)
-    ~Slot() {
-        if (tok) cto_dev_tokeniser_destroy(tok);
-        if (pack) cto_pack_free(pack);
-        if (uploaded) (void)hipEventDestroy(uploaded);
-        if (done) (void)hipEventDestroy(done);
-        if (begin) (void)hipEventDestroy(begin);
-        if (computed) (void)hipEventDestroy(computed);
-        if (kernels_end) (void)hipEventDestroy(kernels_end);
+    int open(int dev) {
+        device = dev;
+        int rc;
+        if ((rc = uploaded.create(hipEventDisableTiming)) || (rc = begin.create()) || (rc = computed.create(hipEventDisableTiming)) ||
+            (rc = kernels_end.create()) || (rc = done.create(hipEventBlockingSync)))      // writers sleep, not spin, until their chunk is back
+            return rc;
+        return CTO_OK;
     }
+    void drop_pack() { if (pack) { cto_pack_free(pack); pack = nullptr; } }
+    ~Slot() { if (tok) cto_dev_tokeniser_destroy(tok); drop_pack(); }
 };
 
 // One chunk's trip through the device inflate (csrc/inflate.hip): the BGZF byte range + block table in page-locked memory, their
@@ -92,233 +108,19 @@ struct Slot {
 struct InflateCtx {
     cto_dev_pileup* pile = nullptr;      // reads -> columns on the device (csrc/pileup.hip), created on first use
     int device = 0, cus = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t landed = nullptr;         // recorded behind the copy back; the producer thread sleeps on it (wait_event)
     PinBuf h_in, h_out, h_sites;         // h_sites: the chunk's candidate positions on their way up (page-locked like every copy source)
     DevBuf d_in, d_out;
+    Stream stream;                       // (after the buffers: drained before they are freed)
+    Event landed;                        // recorded behind the copy back; the producer thread sleeps on it (wait_event)
     int open(int dev, int n_cus) {
-        device = dev;
-        cus = n_cus;
+        device = dev; cus = n_cus;
         uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         for (int i = 0; i < n_cus && i < 256; ++i) mask[i / 32] |= 1u << (i % 32);
-        CTO_HIP(hipExtStreamCreateWithCUMask(&stream, 8, mask));
-        CTO_HIP(hipEventCreateWithFlags(&landed, hipEventBlockingSync | hipEventDisableTiming));
-        return CTO_OK;
+        const int rc = stream.create_on_cus(mask, 8);
+        return rc != CTO_OK ? rc : landed.create(hipEventBlockingSync | hipEventDisableTiming);
     }
-    ~InflateCtx() {
-        if (pile) cto_dev_pileup_destroy(pile);
-        if (landed) (void)hipEventDestroy(landed);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
+    ~InflateCtx() { if (pile) cto_dev_pileup_destroy(pile); }
 };
-
-template <class T>
-struct Queue {                            // unbounded MPMC queue with a closed state
-    std::mutex m;
-    std::condition_variable cv;
-    std::deque<T> q;
-    bool closed = false;
-    void push(T v) { { std::lock_guard<std::mutex> g(m); q.push_back(std::move(v)); } cv.notify_one(); }
-    void close() { { std::lock_guard<std::mutex> g(m); closed = true; } cv.notify_all(); }
-    bool try_pop(T* out) {
-        std::lock_guard<std::mutex> g(m);
-        if (q.empty()) return false;
-        *out = std::move(q.front());
-        q.pop_front();
-        return true;
-    }
-    bool pop_for(T* out, int ms) {         // pop() that gives up after `ms` milliseconds
-        std::unique_lock<std::mutex> g(m);
-        if (!cv.wait_for(g, std::chrono::milliseconds(ms), [&] { return !q.empty() || closed; })) return false;
-        if (q.empty()) return false;
-        *out = std::move(q.front());
-        q.pop_front();
-        return true;
-    }
-    bool pop(T* out) {
-        std::unique_lock<std::mutex> g(m);
-        cv.wait(g, [&] { return !q.empty() || closed; });
-        if (q.empty()) return false;
-        *out = std::move(q.front());
-        q.pop_front();
-        return true;
-    }
-};
-
-struct Mapped {                           // a file's bytes: mapped read-only, or - for a *.gz path - inflated into memory (zlib)
-    const char* p = nullptr;
-    size_t n = 0;
-    std::vector<char> owned;
-    // sniff = true: look at the first two bytes instead of the name (`gzip -fdc`, which the reference's bed_tree_from pipes every BED
-    // through, shared/interval_tree.py:43, inflates what is gzip and passes on what is not)
-    bool open(const char* path, std::string* err, bool sniff = false) {
-        const size_t pl = strlen(path);
-        bool gz = pl > 3 && strcmp(path + pl - 3, ".gz") == 0;        // the reference's readers gzip.open such files
-        if (sniff && !gz) {
-            const int fd0 = ::open(path, O_RDONLY | O_CLOEXEC);
-            if (fd0 < 0) { *err = std::string("cannot open ") + path; return false; }
-            unsigned char magic[2] = {0, 0};
-            const ssize_t got = ::read(fd0, magic, 2);
-            ::close(fd0);
-            gz = got == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
-        }
-        if (gz) {
-            gzFile g = gzopen(path, "rb");
-            if (!g) { *err = std::string("cannot open ") + path; return false; }
-            (void)gzbuffer(g, 1 << 20);
-            owned.resize(size_t(1) << 22);
-            size_t got = 0;
-            for (;;) {
-                if (got == owned.size()) owned.resize(owned.size() * 2);
-                const int r = gzread(g, owned.data() + got, unsigned(std::min<size_t>(owned.size() - got, size_t(1) << 30)));
-                if (r < 0) { gzclose(g); *err = std::string("cannot inflate ") + path; return false; }
-                if (r == 0) break;
-                got += size_t(r);
-            }
-            gzclose(g);
-            owned.resize(got);
-            p = got ? owned.data() : nullptr;
-            n = got;
-            return true;
-        }
-        const int fd = ::open(path, O_RDONLY | O_CLOEXEC);
-        if (fd < 0) { *err = std::string("cannot open ") + path; return false; }
-        struct stat st;
-        if (fstat(fd, &st) != 0) { ::close(fd); *err = std::string("cannot stat ") + path; return false; }
-        n = size_t(st.st_size);
-        if (n) {
-            void* m = mmap(nullptr, n, PROT_READ, MAP_PRIVATE, fd, 0);
-            if (m == MAP_FAILED) { ::close(fd); n = 0; *err = std::string("cannot map ") + path; return false; }
-            p = static_cast<const char*>(m);
-        }
-        ::close(fd);
-        return true;
-    }
-    ~Mapped() { if (p && n && owned.empty()) munmap(const_cast<char*>(p), n); }
-};
-
-// stdout of `argv` (a `samtools mpileup ...` command line) into `out`; false + *err when it cannot be started or exits non-zero
-// (create_tensor_pileup_calling.py:426-446 pipes the same command; subprocess.run(check=True) in the Python mirror)
-bool capture_stdout(const std::vector<std::string>& argv, std::vector<char>* out, std::string* err) {
-    int fds[2];
-    if (pipe2(fds, O_CLOEXEC) != 0) { *err = "pipe() failed"; return false; }
-    posix_spawn_file_actions_t fa;
-    posix_spawn_file_actions_init(&fa);
-    posix_spawn_file_actions_adddup2(&fa, fds[1], 1);
-    std::vector<char*> av;
-    for (const std::string& a : argv) av.push_back(const_cast<char*>(a.c_str()));
-    av.push_back(nullptr);
-    pid_t pid = 0;
-    const int rc = posix_spawnp(&pid, av[0], &fa, nullptr, av.data(), environ);
-    posix_spawn_file_actions_destroy(&fa);
-    ::close(fds[1]);
-    if (rc != 0) { ::close(fds[0]); *err = "cannot run " + argv[0] + ": " + strerror(rc); return false; }
-    out->clear();
-    out->resize(size_t(1) << 22);
-    size_t got = 0;
-    for (;;) {
-        if (got == out->size()) out->resize(out->size() * 2);
-        const ssize_t r = read(fds[0], out->data() + got, out->size() - got);
-        if (r < 0 && errno == EINTR) continue;
-        if (r <= 0) break;
-        got += size_t(r);
-    }
-    ::close(fds[0]);
-    out->resize(got);
-    int status = 0;
-    while (waitpid(pid, &status, 0) < 0 && errno == EINTR) {}
-    if (!WIFEXITED(status) || WEXITSTATUS(status) != 0) {
-        *err = argv[0] + " mpileup failed (exit status " + std::to_string(WIFEXITED(status) ? WEXITSTATUS(status) : -1) + ")";
-        return false;
-    }
-    return true;
-}
-
-struct FaiRec { int64_t length = 0, offset = 0, linebases = 0, linewidth = 0; bool ok = false; };
-
-// <fasta>.fai (or <fasta without extension>.fai): the record of contig `ctg`  (fasta.py read_region)
-bool fai_lookup(const std::string& fasta, const std::string& ctg, FaiRec* rec, std::string* err) {
-    std::string fai = fasta + ".fai";
-    FILE* f = fopen(fai.c_str(), "r");
-    if (!f) {
-        const size_t dot = fasta.rfind('.');
-        if (dot != std::string::npos) { fai = fasta.substr(0, dot) + ".fai"; f = fopen(fai.c_str(), "r"); }
-    }
-    if (!f) { *err = "[ERROR] file " + fasta + ".fai not found"; return false; }
-    char line[4096];
-    while (fgets(line, sizeof(line), f)) {
-        char* tab = strchr(line, '\t');
-        if (!tab) continue;
-        if (size_t(tab - line) == ctg.size() && memcmp(line, ctg.data(), ctg.size()) == 0) {
-            long long a = 0, b = 0, c = 0, d = 0;
-            if (sscanf(tab + 1, "%lld\t%lld\t%lld\t%lld", &a, &b, &c, &d) == 4 && c > 0 && d > 0) {
-                rec->length = a; rec->offset = b; rec->linebases = c; rec->linewidth = d; rec->ok = true;
-            }
-            break;
-        }
-    }
-    fclose(f);
-    if (!rec->ok) { *err = "contig " + ctg + " not in " + fai; return false; }
-    return true;
-}
-
-// 1-based inclusive [start, end] of the contig, upper-cased, clipped to the contig (fasta.py read_region)
-bool read_region(const Mapped& fa, const FaiRec& r, int64_t start, int64_t end, std::string* out, std::string* err) {
-    out->clear();
-    if (fa.n >= 2 && (unsigned char)fa.p[0] == 0x1f && (unsigned char)fa.p[1] == 0x8b) {
-        *err = "[ERROR] the reference is gzip / bgzip compressed: decompress it (and re-run samtools faidx) before use";
-        return false;
-    }
-    start = std::max<int64_t>(1, start);
-    end = std::min<int64_t>(r.length, end);
-    if (end < start) return true;
-    const int64_t s0 = start - 1, e0 = end;
-    const int64_t b0 = r.offset + (s0 / r.linebases) * r.linewidth + s0 % r.linebases;
-    const int64_t b1 = r.offset + ((e0 - 1) / r.linebases) * r.linewidth + (e0 - 1) % r.linebases + 1;
-    if (b0 < 0 || b1 > int64_t(fa.n) || b1 < b0) { *err = "reference index points outside the FASTA file"; return false; }
-    out->resize(size_t(end - start + 1));
-    char* dst = &(*out)[0];
-    size_t n = 0;
-    for (const char* q = fa.p + b0; q < fa.p + b1;) {                 // line by line: memchr + one pass that folds the case
-        const char* nl = static_cast<const char*>(memchr(q, '\n', size_t(fa.p + b1 - q)));
-        const char* e = nl ? nl : fa.p + b1;
-        for (const char* c = q; c < e; ++c)
-            if (*c != '\r' && n < out->size()) dst[n++] = (*c >= 'a' && *c <= 'z') ? char(*c - 32) : *c;
-        q = e + 1;
-    }
-    out->resize(n);
-    return true;
-}
-
-// BED rows of `ctg` as 0-based [begin, end) intervals, sorted and merged (what `samtools mpileup -l` restricts positions to)
-void bed_intervals(const char* text, size_t len, const std::string& ctg, std::vector<int64_t>* out) {
-    std::vector<std::pair<int64_t, int64_t>> iv;
-    size_t i = 0;
-    while (i < len) {
-        const char* nl = static_cast<const char*>(memchr(text + i, '\n', len - i));
-        const size_t e = nl ? size_t(nl - text) : len;
-        const char* row = text + i;
-        const size_t rl = e - i;
-        const char* t1 = static_cast<const char*>(memchr(row, '\t', rl));
-        if (t1 && size_t(t1 - row) == ctg.size() && memcmp(row, ctg.data(), ctg.size()) == 0) {
-            const char* t2 = static_cast<const char*>(memchr(t1 + 1, '\t', rl - size_t(t1 + 1 - row)));
-            if (t2) {
-                const long long a = atoll(std::string(t1 + 1, size_t(t2 - t1 - 1)).c_str());
-                const char* t3 = static_cast<const char*>(memchr(t2 + 1, '\t', rl - size_t(t2 + 1 - row)));
-                const size_t l3 = t3 ? size_t(t3 - t2 - 1) : rl - size_t(t2 + 1 - row);
-                const long long b = atoll(std::string(t2 + 1, l3).c_str());
-                iv.emplace_back(std::max<long long>(0, a), b);
-            }
-        }
-        i = e + 1;
-    }
-    std::sort(iv.begin(), iv.end());
-    out->clear();
-    for (const auto& p : iv) {
-        if (!out->empty() && p.first <= (*out)[out->size() - 1]) (*out)[out->size() - 1] = std::max((*out)[out->size() - 1], p.second);
-        else { out->push_back(p.first); out->push_back(p.second); }
-    }
-}
 
 __global__ void k_gather_rows(const int16_t* __restrict__ colvec, const int32_t* __restrict__ site_info, int64_t n, int16_t* __restrict__ out) {
     const int64_t i = blockIdx.x;
@@ -328,33 +130,86 @@ __global__ void k_gather_rows(const int16_t* __restrict__ colvec, const int32_t*
     if (threadIdx.x < CTO_COLVEC_STRIDE) out[i * CTO_COLVEC_STRIDE + threadIdx.x] = colvec[col * CTO_COLVEC_STRIDE + threadIdx.x];
 }
 
+// Slots (device + page-locked buffers, events) and device-inflate contexts outlive the call: allocating and freeing ~100 MB of them
+// per slot costs tens of milliseconds, which a short chunk list would pay on every call; cto_run_release() frees them.
 // never destroyed: at process exit the HIP runtime may already be gone when static destructors run
 std::mutex& slot_cache_m() { static std::mutex* m = new std::mutex(); return *m; }
 std::vector<std::unique_ptr<Slot>>& slot_cache() { static auto* v = new std::vector<std::unique_ptr<Slot>>(); return *v; }
 std::vector<std::unique_ptr<InflateCtx>>& inflate_cache() { static auto* v = new std::vector<std::unique_ptr<InflateCtx>>(); return *v; }
-struct SlotReturn {                      // hands a finished (or failed) call's slots back to the cache
-    std::vector<std::unique_ptr<Slot>>* slots;
-    ~SlotReturn() {
-        std::lock_guard<std::mutex> g(slot_cache_m());
-        for (auto& sl : *slots) {
-            if (sl->pack) { cto_pack_free(sl->pack); sl->pack = nullptr; }
-            slot_cache().push_back(std::move(sl));
-        }
-        slots->clear();
-    }
-};
 
-struct CtxReturn {
-    std::vector<std::unique_ptr<InflateCtx>>* ctx;
-    ~CtxReturn() {
+// A call's share of a cache: up to `want` entries that `fits` move out of it; however the call ends, all of its own go (back) in
+template <class T>
+struct Lease {
+    std::vector<std::unique_ptr<T>>& cache;
+    std::vector<std::unique_ptr<T>>* mine;
+    void (*before_return)(T&);               // what an entry lets go of first (may be null)
+    template <class Fits>
+    void take(int want, Fits fits) {
         std::lock_guard<std::mutex> g(slot_cache_m());
-        for (auto& c : *ctx) inflate_cache().push_back(std::move(c));
-        ctx->clear();
+        for (size_t i = 0; i < cache.size() && int(mine->size()) < want;)
+            if (fits(*cache[i])) { mine->push_back(std::move(cache[i])); cache.erase(cache.begin() + long(i)); }
+            else ++i;
+    }
+    ~Lease() {
+        std::lock_guard<std::mutex> g(slot_cache_m());
+        for (auto& x : *mine) { if (before_return) before_return(*x); cache.push_back(std::move(x)); }
+        mine->clear();
     }
 };
 
 constexpr int FLANK_POS = 33, EXPAND_REF = 1000;       // shared/param.py no_of_positions, expand_reference_region
 constexpr int REGION_FLANK = 17;                       // flankingBaseNum + 1: the window columns of a candidate at the edge of a region
+
+// A pack in a slot's device buffer: its seven arrays + the chunk's candidate positions in ONE allocation, each part 256-byte aligned
+// with 256 bytes behind it.  The page-locked staging buffer of the upload path has the same layout.
+struct PackLayout {
+    enum { SITES = 7, PARTS = 8 };
+    const void* src[PARTS];              // where the parts come from: the arrays of `v` (host or device) and the site list
+    size_t bytes[PARTS], off[PARTS], total = 0;
+    PackLayout(const cto_pack_view& v, const void* sites, size_t n_sites)
+        : src{v.entries, v.col_pos, v.col_ref, v.col_off, v.key_off, v.key_meta, v.key_group, sites} {
+        const size_t nc = size_t(v.n_cols), ne = size_t(v.n_entries), nk = size_t(v.n_keys);
+        const size_t b[PARTS] = {ne * 4, nc * 4, nc, (nc + 1) * 8, (nc + 1) * 4, nk, nk * 4, n_sites * 4};
+        for (int i = 0; i < PARTS; ++i) { bytes[i] = b[i]; off[i] = total; total += (b[i] + 255) / 256 * 256 + 256; }
+    }
+    // the pointers of `v` (its counts are the caller's) and the site list, in the allocation at `base`
+    void bind(const void* base, cto_pack_view* v, const int32_t** d_site_pos) const {
+        const char* d = static_cast<const char*>(base);
+        v->entries = reinterpret_cast<const uint32_t*>(d + off[0]);
+        v->col_pos = reinterpret_cast<const int32_t*>(d + off[1]);
+        v->col_ref = reinterpret_cast<const uint8_t*>(d + off[2]);
+        v->col_off = reinterpret_cast<const int64_t*>(d + off[3]);
+        v->key_off = reinterpret_cast<const int32_t*>(d + off[4]);
+        v->key_meta = reinterpret_cast<const uint8_t*>(d + off[5]);
+        v->key_group = reinterpret_cast<const int32_t*>(d + off[6]);
+        *d_site_pos = reinterpret_cast<const int32_t*>(d + off[SITES]);
+    }
+};
+
+// A pack born on the device (pile-up, tokeniser) becomes the slot's: its arrays `dvw` move from the context that made them into the slot's
+// one device allocation, laid out as the upload path lays it out, + the candidate positions out of `site_stage`; `lite` is the host's part.
+// s->uploaded is recorded; `wait_on` (that event, or one recorded right behind it) is waited for: context and `site_stage` are free again.
+int adopt_device_pack(Slot* s, const cto_pack_view& dvw, cto_pack* lite, PinBuf& site_stage, hipStream_t stream, hipEvent_t wait_on) {
+    const size_t ns = s->sites.size();
+    int rc = site_stage.ensure(ns * 4 + 256);
+    const PackLayout lay(dvw, site_stage.p, ns);
+    if (rc != CTO_OK || (rc = s->pack_dev.ensure(lay.total)) != CTO_OK) { cto_pack_free(lite); return rc; }
+    memcpy(site_stage.p, s->sites.data(), ns * 4);
+    char* d = static_cast<char*>(s->pack_dev.p);
+    for (int i = 0; i < PackLayout::PARTS; ++i)
+        if (lay.bytes[i])
+            CTO_HIP(hipMemcpyAsync(d + lay.off[i], lay.src[i], lay.bytes[i], i == PackLayout::SITES ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, stream));
+    if (s->pack) cto_pack_free(s->pack);
+    s->pack = lite;
+    s->hv = cto_pack_view{};
+    s->hv.n_cols = dvw.n_cols; s->hv.n_entries = dvw.n_entries; s->hv.n_keys = dvw.n_keys;
+    s->dv = s->hv;
+    lay.bind(d, &s->dv, &s->d_site_pos);
+    CTO_HIP(hipEventRecord(s->uploaded, stream));
+    if (wait_on != s->uploaded.e) CTO_HIP(hipEventRecord(wait_on, stream));
+    CTO_HIP(wait_event(wait_on));
+    return CTO_OK;
+}
 
 struct Run {
     const cto_run_cfg* cfg;
@@ -368,52 +223,15 @@ struct Run {
     std::atomic<bool> failed{false};
     std::atomic<int64_t> candidates{0}, sites{0}, rows{0}, low_cov{0}, clamped{0};
     std::mutex stat_m;
-    double produce_s = 0, finish_s = 0, pack_s = 0, upload_s = 0, device_s = 0;
+    cto_run_stats st{};                  // its times (under stat_m, the launcher's are its own); the counters are added at the end
     Mapped fasta;
     std::vector<std::unique_ptr<InflateCtx>> inflate_ctx;
     Queue<InflateCtx*> free_ctx;
     std::atomic<int64_t> device_inflated{0}, device_piled{0}, device_tokenised{0};
     std::mutex fai_m;
     std::map<std::string, FaiRec> fai;
-    // --call_indels_only_in_these_regions: per contig the rows as sorted, merged [begin, end) intervals (bed_tree_from of the reference)
+    // --call_indels_only_in_these_regions: per contig the rows as sorted, merged [begin, end) intervals (run_files.h load_indel_regions)
     std::map<std::string, std::vector<int64_t>> indel_regions;
-    bool load_indel_regions(std::string* err) {
-        if (!cfg->indel_regions_bed || !cfg->indel_regions_bed[0]) return true;
-        Mapped bed;
-        if (!bed.open(cfg->indel_regions_bed, err, /*sniff=*/true)) return false;
-        std::map<std::string, std::vector<std::pair<int64_t, int64_t>>> rows;
-        size_t i = 0;
-        int64_t row_id = 0;
-        while (i < bed.n) {
-            ++row_id;
-            const char* nl = static_cast<const char*>(memchr(bed.p + i, '\n', bed.n - i));
-            const size_t e = nl ? size_t(nl - bed.p) : bed.n;
-            std::string row(bed.p + i, e - i);
-            i = e + 1;
-            if (row.empty() || row[0] == '#') continue;
-            char name[256];
-            long long a = 0, b = 0;
-            if (row.find_first_not_of(" \t\r") == std::string::npos) continue;
-            // a row the reference cannot split into name, start, end ends its run with an exception (interval_tree.py:47-55): an
-            // unreadable BED must not turn into "no regions", which would let every indel candidate through
-            if (sscanf(row.c_str(), "%255s %lld %lld", name, &a, &b) != 3) {
-                *err = "[ERROR] Invalid bed input in " + std::to_string(row_id) + "-th row of " + std::string(cfg->indel_regions_bed) + ": " + row.substr(0, 80);
-                return false;
-            }
-            if (b < a || a < 0 || b < 0) { *err = "[ERROR] Invalid bed input in " + std::string(cfg->indel_regions_bed) + ": " + row; return false; }
-            if (a == b) ++b;
-            rows[name].emplace_back(a, b);
-        }
-        for (auto& kv : rows) {
-            std::sort(kv.second.begin(), kv.second.end());
-            std::vector<int64_t>& out = indel_regions[kv.first];
-            for (const auto& p : kv.second) {
-                if (!out.empty() && p.first <= out.back()) out.back() = std::max(out.back(), p.second);
-                else { out.push_back(p.first); out.push_back(p.second); }
-            }
-        }
-        return true;
-    }
     bool fai_of(const std::string& ctg, FaiRec* rec, std::string* err) {
         std::lock_guard<std::mutex> g(fai_m);
         auto it = fai.find(ctg);
@@ -446,16 +264,9 @@ struct Run {
         size_t cap = nbytes / 2048 + 64;
         if ((rc = c->h_in.ensure(in_al + cap * sizeof(cto_bgzf_block))) != CTO_OK) return rc;
         {
-            const int fd = ::open(j.bam_path, O_RDONLY | O_CLOEXEC);
-            CTO_REQUIRE(fd >= 0, CTO_EINVAL, "cannot open %s", j.bam_path);
-            size_t got = 0;
-            while (got < nbytes) {
-                const ssize_t r = pread(fd, static_cast<char*>(c->h_in.p) + got, nbytes - got, off_t(fb) + off_t(got));
-                if (r <= 0) break;
-                got += size_t(r);
-            }
-            ::close(fd);
-            CTO_REQUIRE(got == nbytes, CTO_EINVAL, "short read from %s", j.bam_path);
+            const File f(j.bam_path);
+            CTO_REQUIRE(f.ok(), CTO_EINVAL, "cannot open %s", j.bam_path);
+            CTO_REQUIRE(read_exact(f.fd, c->h_in.p, nbytes, fb), CTO_EINVAL, "short read from %s", j.bam_path);
         }
         const double T1 = now_s(), C1 = cpu_s();
         int64_t n = 0, out_bytes = 0;
@@ -472,6 +283,13 @@ struct Run {
         const auto* blocks = reinterpret_cast<const cto_bgzf_block*>(static_cast<char*>(c->h_in.p) + in_al);
         const size_t tbl = size_t(n) * sizeof(cto_bgzf_block), out_al = (size_t(std::max<int64_t>(out_bytes, 256)) + 255) / 256 * 256;
         if ((rc = c->d_in.ensure(in_al + tbl)) || (rc = c->d_out.ensure(out_al + size_t(n) * 4)) || (rc = c->h_out.ensure(out_al + size_t(n) * 4))) return rc;
+        const auto all_inflated = [&]() -> int {      // the blocks' status words, once they are back in h_out
+            const int* status = reinterpret_cast<const int*>(static_cast<char*>(c->h_out.p) + out_al);
+            for (int64_t b = 0; b < n; ++b)
+                CTO_REQUIRE(status[b] == 0, CTO_EINVAL, "%s: the BGZF block at file offset %llu does not inflate (status %d)", j.bam_path,
+                            (unsigned long long)blocks[b].file_off, status[b]);
+            return CTO_OK;
+        };
         const double T2 = now_s(), C2 = cpu_s();
         CTO_HIP(hipMemcpyAsync(c->d_in.p, c->h_in.p, in_al + tbl, hipMemcpyHostToDevice, c->stream));
         if ((rc = cto_bgzf_inflate(c->d_in.p, reinterpret_cast<const cto_bgzf_block*>(static_cast<char*>(c->d_in.p) + in_al), int(n), c->d_out.p,
@@ -482,10 +300,7 @@ struct Run {
             CTO_HIP(hipMemcpyAsync(static_cast<char*>(c->h_out.p) + out_al, static_cast<char*>(c->d_out.p) + out_al, size_t(n) * 4, hipMemcpyDeviceToHost, c->stream));
             CTO_HIP(hipEventRecord(c->landed, c->stream));
             CTO_HIP(wait_event(c->landed));
-            const int* st0 = reinterpret_cast<const int*>(static_cast<char*>(c->h_out.p) + out_al);
-            for (int64_t b = 0; b < n; ++b)
-                CTO_REQUIRE(st0[b] == 0, CTO_EINVAL, "%s: the BGZF block at file offset %llu does not inflate (status %d)", j.bam_path,
-                            (unsigned long long)blocks[b].file_off, st0[b]);
+            if ((rc = all_inflated()) != CTO_OK) return rc;
             if (!c->pile && (rc = cto_dev_pileup_create(&c->pile))) return rc;
             std::vector<uint64_t> voffs(size_t(4096 + ((hi - lo) >> 14) + 64));
             int32_t tid = -1;
@@ -504,36 +319,7 @@ struct Run {
                 if (rc != CTO_OK) return rc;
             }
             if (!fallback) {
-                // the pack's arrays move from the context (re-used by the next chunk) into the slot's one device allocation, laid out
-                // as the upload path lays it out, + the candidate positions
-                const size_t nc = size_t(dvw.n_cols), ne = size_t(dvw.n_entries), nk = size_t(dvw.n_keys), ns = s->sites.size();
-                if ((rc = c->h_sites.ensure(s->sites.size() * 4 + 4)) != CTO_OK) { cto_pack_free(lite); return rc; }
-                memcpy(c->h_sites.p, s->sites.data(), s->sites.size() * 4);
-                const void* src[8] = {dvw.entries, dvw.col_pos, dvw.col_ref, dvw.col_off, dvw.key_off, dvw.key_meta, dvw.key_group, c->h_sites.p};
-                const size_t bytes[8] = {ne * 4, nc * 4, nc, (nc + 1) * 8, (nc + 1) * 4, nk, nk * 4, ns * 4};
-                size_t off[8], total = 0;
-                for (int i = 0; i < 8; ++i) { off[i] = total; total += (bytes[i] + 255) / 256 * 256 + 256; }
-                if ((rc = s->pack_dev.ensure(total)) != CTO_OK) { cto_pack_free(lite); return rc; }
-                char* d = static_cast<char*>(s->pack_dev.p);
-                for (int i = 0; i < 8; ++i)
-                    if (bytes[i])
-                        CTO_HIP(hipMemcpyAsync(d + off[i], src[i], bytes[i], i == 7 ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
-                if (s->pack) cto_pack_free(s->pack);
-                s->pack = lite;
-                s->hv = cto_pack_view{};
-                s->hv.n_cols = dvw.n_cols; s->hv.n_entries = dvw.n_entries; s->hv.n_keys = dvw.n_keys;
-                s->dv = s->hv;
-                s->dv.entries = reinterpret_cast<const uint32_t*>(d + off[0]);
-                s->dv.col_pos = reinterpret_cast<const int32_t*>(d + off[1]);
-                s->dv.col_ref = reinterpret_cast<const uint8_t*>(d + off[2]);
-                s->dv.col_off = reinterpret_cast<const int64_t*>(d + off[3]);
-                s->dv.key_off = reinterpret_cast<const int32_t*>(d + off[4]);
-                s->dv.key_meta = reinterpret_cast<const uint8_t*>(d + off[5]);
-                s->dv.key_group = reinterpret_cast<const int32_t*>(d + off[6]);
-                s->d_site_pos = reinterpret_cast<const int32_t*>(d + off[7]);
-                CTO_HIP(hipEventRecord(s->uploaded, c->stream));
-                CTO_HIP(hipEventRecord(c->landed, c->stream));
-                CTO_HIP(wait_event(c->landed));               // the context (and s->sites' bytes) are free for the next chunk
+                if ((rc = adopt_device_pack(s, dvw, lite, c->h_sites, c->stream, c->landed)) != CTO_OK) return rc;
                 if (timing)
                     fprintf(stderr, "device pile-up: %.1f MB in %lld blocks -> %lld columns, %lld entries: read %.1f ms, inflate + pile-up %.1f; thread CPU: span %.1f ms, read %.1f, scan %.1f, rest %.1f\n", nbytes / 1e6,
                             (long long)n, (long long)dvw.n_cols, (long long)dvw.n_entries, (T1 - T0) * 1e3, (now_s() - T2) * 1e3, (Cs - C0) * 1e3, (C1 - Cs) * 1e3, (C2 - C1) * 1e3, (cpu_s() - C2) * 1e3);
@@ -548,10 +334,7 @@ struct Run {
         const double T3 = now_s();
         CTO_HIP(wait_event(c->landed));
         const double T4 = now_s();
-        const int* status = reinterpret_cast<const int*>(static_cast<char*>(c->h_out.p) + out_al);
-        for (int64_t b = 0; b < n; ++b)
-            CTO_REQUIRE(status[b] == 0, CTO_EINVAL, "%s: the BGZF block at file offset %llu does not inflate (status %d)", j.bam_path,
-                        (unsigned long long)blocks[b].file_off, status[b]);
+        if ((rc = all_inflated()) != CTO_OK) return rc;
         rc = cto_pack_from_bam_inflated(j.bam_path, nullptr, ctg.c_str(), lo, hi, iv.empty() ? nullptr : iv.data(), int64_t(iv.size() / 2), s->ref.data(),
                                         s->ref_start, s->ref.size(), 2316, 0, cfg->max_depth, cfg->max_indel_length,
                                         static_cast<const uint8_t*>(c->h_out.p), size_t(out_bytes), blocks, n, &s->pack);
@@ -562,49 +345,99 @@ struct Run {
         return rc;
     }
 
-    // mpileup text -> pack on the device (cto_tokenise_device): `text` is host memory (the slot's tokeniser buffer when the file was read
-    // straight into it).  *done = 1: the pack sits in the slot's device buffers in the layout of the upload path, s->pack is the host's
-    // lite part, s->uploaded is recorded; *done = 0: the text is one the single pass declines - the caller tokenises it on the host.
-    int pack_from_text_device(Slot* s, const char* text, size_t len, hipStream_t stream, int* done) {
-        *done = 0;
+    // mpileup text (a mapped file, the slot's tokeniser buffer, samtools' output) -> the slot's pack: on the device where that is configured
+    // and the text is one the single pass of cto_tokenise_device takes (*on_device: as adopt_device_pack leaves it), else on the host
+    int pack_from_text(Slot* s, const char* text, size_t len, hipStream_t stream, bool* on_device) {
+        *on_device = false;
         int rc;
-        if (!s->tok && (rc = cto_dev_tokeniser_create(&s->tok))) return rc;
-        cto_pack_view dvw{};
-        cto_pack* lite = nullptr;
-        int fallback = 0;
-        if ((rc = cto_tokenise_device(s->tok, text, len, s->ref.data(), s->ref_start, s->ref.size(), cfg->max_indel_length, stream, &dvw, &lite, &fallback)))
-            return rc;
-        if (fallback) return CTO_OK;
-        const size_t nc = size_t(dvw.n_cols), ne = size_t(dvw.n_entries), nk = size_t(dvw.n_keys), ns = s->sites.size();
-        if ((rc = s->stage.ensure(ns * 4 + 256)) != CTO_OK) { cto_pack_free(lite); return rc; }
-        memcpy(s->stage.p, s->sites.data(), ns * 4);
-        const void* src[8] = {dvw.entries, dvw.col_pos, dvw.col_ref, dvw.col_off, dvw.key_off, dvw.key_meta, dvw.key_group, s->stage.p};
-        const size_t bytes[8] = {ne * 4, nc * 4, nc, (nc + 1) * 8, (nc + 1) * 4, nk, nk * 4, ns * 4};
-        size_t off[8], total = 0;
-        for (int i = 0; i < 8; ++i) { off[i] = total; total += (bytes[i] + 255) / 256 * 256 + 256; }
-        if ((rc = s->pack_dev.ensure(total)) != CTO_OK) { cto_pack_free(lite); return rc; }
-        char* d = static_cast<char*>(s->pack_dev.p);
-        for (int i = 0; i < 8; ++i)
-            if (bytes[i]) CTO_HIP(hipMemcpyAsync(d + off[i], src[i], bytes[i], i == 7 ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, stream));
-        if (s->pack) cto_pack_free(s->pack);
-        s->pack = lite;
-        s->hv = cto_pack_view{};
-        s->hv.n_cols = dvw.n_cols; s->hv.n_entries = dvw.n_entries; s->hv.n_keys = dvw.n_keys;
-        s->dv = s->hv;
-        s->dv.entries = reinterpret_cast<const uint32_t*>(d + off[0]);
-        s->dv.col_pos = reinterpret_cast<const int32_t*>(d + off[1]);
-        s->dv.col_ref = reinterpret_cast<const uint8_t*>(d + off[2]);
-        s->dv.col_off = reinterpret_cast<const int64_t*>(d + off[3]);
-        s->dv.key_off = reinterpret_cast<const int32_t*>(d + off[4]);
-        s->dv.key_meta = reinterpret_cast<const uint8_t*>(d + off[5]);
-        s->dv.key_group = reinterpret_cast<const int32_t*>(d + off[6]);
-        s->d_site_pos = reinterpret_cast<const int32_t*>(d + off[7]);
-        CTO_HIP(hipEventRecord(s->uploaded, stream));
-        CTO_HIP(wait_event(s->uploaded));              // the site list left the staging buffer; the tokeniser's arrays are free for the next chunk
-        *done = 1;
-        ++device_tokenised;
-        return CTO_OK;
+        if (cfg->device_tokenise && len > 0) {
+            cto_pack_view dvw{};
+            cto_pack* lite = nullptr;
+            int fallback = 0;
+            if (!s->tok && (rc = cto_dev_tokeniser_create(&s->tok))) return rc;
+            if ((rc = cto_tokenise_device(s->tok, text, len, s->ref.data(), s->ref_start, s->ref.size(), cfg->max_indel_length, stream, &dvw, &lite, &fallback)))
+                return rc;
+            if (!fallback) {
+                // waiting for s->uploaded: the site list left the staging buffer; the tokeniser's arrays are free for the next chunk
+                if ((rc = adopt_device_pack(s, dvw, lite, s->stage, stream, s->uploaded)) != CTO_OK) return rc;
+                *on_device = true;
+                ++device_tokenised;
+                return CTO_OK;
+            }
+        }
+        // the tokeniser's threads merge their entries straight into the staging buffer (a read-base is >= 3 characters of text)
+        const size_t ecap = len / 3 + 4096;
+        if ((rc = s->stage.ensure(ecap * 4 + len / 4 + (size_t(1) << 20))) != CTO_OK) return rc;
+        return pack_from_mpileup_impl(len ? text : "", len, s->ref.data(), s->ref_start, s->ref.size(), cfg->max_indel_length,
+                                      static_cast<uint32_t*>(s->stage.p), ecap, &s->pack);
     }
+
+    // the pack of a chunk whose pileup is a text file; false: failed (the error is recorded)
+    bool pack_from_text_file(Slot* s, const cto_chunk_job& j, hipStream_t stream, bool* on_device) {
+        const size_t pl = strlen(j.mpileup_path);
+        const bool gz = pl > 3 && strcmp(j.mpileup_path + pl - 3, ".gz") == 0;
+        int rc;
+        if (cfg->device_tokenise && !gz) {
+            // the file is read straight into the tokeniser's page-locked buffer: no mapping, no staging copy
+            if (!s->tok && cto_dev_tokeniser_create(&s->tok) != CTO_OK) { fail(cto_last_error()); return false; }
+            const File f(j.mpileup_path);
+            if (!f.ok()) { fail(std::string("cannot open ") + j.mpileup_path); return false; }
+            size_t tn = 0;
+            if (!f.size(&tn)) { fail(std::string("cannot stat ") + j.mpileup_path); return false; }
+            char* buf = cto_dev_tokeniser_buffer(s->tok, tn + 1);
+            if (!buf) { fail(cto_last_error()); return false; }
+            if (!read_exact(f.fd, buf, tn, 0)) { fail(std::string("short read of ") + j.mpileup_path); return false; }
+            rc = pack_from_text(s, buf, tn, stream, on_device);
+        } else {
+            Mapped txt;
+            std::string err;
+            if (!txt.open(j.mpileup_path, &err)) { fail(err); return false; }
+            rc = pack_from_text(s, txt.p, txt.n, stream, on_device);
+        }
+        if (rc != CTO_OK) { fail(cto_last_error()); return false; }
+        return true;
+    }
+
+    // the pack of a chunk piled up from the BAM (lo..hi, only `iv` when not empty) by a samtools child, the device or the host reader
+    bool pack_from_alignments(Slot* s, const cto_chunk_job& j, const std::string& ctg, bool region_job, int64_t lo, int64_t hi, const std::vector<int64_t>& iv,
+                              hipStream_t stream, bool* on_device) {
+        int rc = CTO_OK;
+        if (cfg->samtools) {
+            // the reference's own producer: `samtools mpileup` with --min-BQ 0 (one pileup serves both passes), its text tokenised
+            std::vector<std::string> cmd = {cfg->samtools, "mpileup", "--reverse-del", "--output-MQ", "-r",
+                                            ctg + ":" + std::to_string(lo) + "-" + std::to_string(hi), "--min-MQ", "0", "--min-BQ", "0"};
+            if (!region_job) { cmd.push_back("-l"); cmd.push_back(j.bed_path); }      // the reference's order of options
+            cmd.push_back("--excl-flags");
+            cmd.push_back("2316");
+            if (cfg->samtools_max_depth > 0) { cmd.push_back("--max-depth"); cmd.push_back(std::to_string(cfg->samtools_max_depth)); }
+            cmd.push_back(j.bam_path);
+            std::vector<char> text;
+            std::string err;
+            if (!capture_stdout(cmd, &text, &err)) { fail(err); return false; }
+            rc = pack_from_text(s, text.data(), text.size(), stream, on_device);
+        } else {
+            InflateCtx* c = nullptr;
+            int done = 0;
+            // a device-inflate context is free: this chunk's blocks go to the GPU.  A REGION job waits for one: piled up at every
+            // position it is seven times a BED chunk's work, which the host reader needs most of a second of a core for
+            // A BED chunk does not wait (CTO_CTX_WAIT_MS, default 0): measured with 96 chunks, waiting 0 / 10 / 20 / 40 ms for a context
+            // sends 68 / 72 / 72 / 80 of them through the device and gives 667 / 654 / 646 / 612 k sites/s - for BED chunks the device
+            // is the busier side, the cores take what it cannot
+            static const int ctx_wait_ms = [] { const char* e = getenv("CTO_CTX_WAIT_MS"); return e ? atoi(e) : 0; }();
+            if (free_ctx.pop(&c, inflate_ctx.empty() ? 0 : region_job && cfg->device_pileup ? -1 : std::max(ctx_wait_ms, 0))) {
+                rc = pack_from_bam_device(j, ctg, lo, hi, iv, s, c, &done);
+                free_ctx.push(c);
+                *on_device = rc == CTO_OK && done == 2;
+            }
+            if (!done && rc == CTO_OK)
+                rc = cto_pack_from_bam(j.bam_path, nullptr, ctg.c_str(), lo, hi, iv.empty() ? nullptr : iv.data(), int64_t(iv.size() / 2),
+                                       s->ref.data(), s->ref_start, s->ref.size(), 2316, 0, cfg->max_depth, cfg->max_indel_length, &s->pack);
+        }
+        if (rc != CTO_OK) { fail(cto_last_error()); return false; }
+        return true;
+    }
+
+    bool nothing_to_call(const cto_chunk_job& j) { if (cfg->verbose) fprintf(stderr, "[INFO] %s total processed positions: 0\n", j.ctg_name); return false; }
 
     // host half of a chunk + the upload; false = nothing to call in this chunk (no output) or an error (failed is set)
     bool produce(Slot* s, hipStream_t stream) {
@@ -634,10 +467,7 @@ struct Run {
             centres.erase(std::unique(centres.begin(), centres.end()), centres.end());
             s->sites.swap(centres);
             candidates += int64_t(s->sites.size());
-            if (s->sites.empty()) {
-                if (cfg->verbose) fprintf(stderr, "[INFO] %s total processed positions: 0\n", j.ctg_name);
-                return false;
-            }
+            if (s->sites.empty()) return nothing_to_call(j);
             ctg_start = span[0];
             ctg_end = span[1];
         }
@@ -645,137 +475,53 @@ struct Run {
         FaiRec fr;
         if (!fai_of(ctg, &fr, &err) || !read_region(fasta, fr, s->ref_start, ctg_end + EXPAND_REF, &s->ref, &err)) { fail(err); return false; }
         if (s->ref.empty()) { fail(std::string("[ERROR] Failed to load reference sequence from file (") + cfg->ref_fa + ")."); return false; }
-        if (s->pack) { cto_pack_free(s->pack); s->pack = nullptr; }
-        int rc = CTO_OK;
+        s->drop_pack();
         bool piled_on_device = false;
         const double t_pack = now_s();
         if (j.mpileup_path) {
-            const size_t pl = strlen(j.mpileup_path);
-            const bool gz = pl > 3 && strcmp(j.mpileup_path + pl - 3, ".gz") == 0;
-            int on_dev = 0;
-            const char* tp = nullptr;
-            size_t tn = 0;
-            Mapped txt;
-            if (cfg->device_tokenise && !gz) {
-                // the file is read straight into the tokeniser's page-locked buffer: no mapping, no staging copy
-                if (!s->tok && (rc = cto_dev_tokeniser_create(&s->tok)) != CTO_OK) { fail(cto_last_error()); return false; }
-                const int fd = ::open(j.mpileup_path, O_RDONLY | O_CLOEXEC);
-                if (fd < 0) { fail(std::string("cannot open ") + j.mpileup_path); return false; }
-                struct stat st;
-                if (fstat(fd, &st) != 0) { ::close(fd); fail(std::string("cannot stat ") + j.mpileup_path); return false; }
-                tn = size_t(st.st_size);
-                char* buf = cto_dev_tokeniser_buffer(s->tok, tn + 1);
-                if (!buf) { ::close(fd); fail(cto_last_error()); return false; }
-                size_t got = 0;
-                while (got < tn) {
-                    const ssize_t r = ::pread(fd, buf + got, tn - got, off_t(got));
-                    if (r <= 0) break;
-                    got += size_t(r);
-                }
-                ::close(fd);
-                if (got != tn) { fail(std::string("short read of ") + j.mpileup_path); return false; }
-                tp = buf;
-                rc = pack_from_text_device(s, tp, tn, stream, &on_dev);
-            } else {
-                if (!txt.open(j.mpileup_path, &err)) { fail(err); return false; }
-                tp = txt.p ? txt.p : "";
-                tn = txt.n;
-                if (cfg->device_tokenise) rc = pack_from_text_device(s, tp, tn, stream, &on_dev);
-            }
-            if (rc == CTO_OK && on_dev) piled_on_device = true;
-            else if (rc == CTO_OK) {
-                // the tokeniser's threads merge their entries straight into the staging buffer (a read-base is >= 3 characters of text)
-                const size_t ecap = tn / 3 + 4096;
-                if (s->stage.ensure(ecap * 4 + tn / 4 + (size_t(1) << 20)) != CTO_OK) { fail(cto_last_error()); return false; }
-                rc = pack_from_mpileup_impl(tp, tn, s->ref.data(), s->ref_start, s->ref.size(), cfg->max_indel_length,
-                                            static_cast<uint32_t*>(s->stage.p), ecap, &s->pack);
-            }
+            if (!pack_from_text_file(s, j, stream, &piled_on_device)) return false;
         } else {
             std::vector<int64_t> iv;                               // REGION job: every position of the range (no -l)
             if (!region_job) bed_intervals(bed.p ? bed.p : "", bed.n, ctg, &iv);
             // REGION job: the candidate range + the flanks of the windows at its edges
             const int64_t lo = region_job ? std::max<int64_t>(1, cand_lo - REGION_FLANK) : std::max<int64_t>(1, ctg_start - FLANK_POS);
             const int64_t hi = region_job ? cand_hi + REGION_FLANK : ctg_end + FLANK_POS;
-            if (cfg->samtools) {
-                // the reference's own producer: `samtools mpileup` with --min-BQ 0 (one pileup serves both passes), its text tokenised
-                std::vector<std::string> cmd = {cfg->samtools, "mpileup", "--reverse-del", "--output-MQ", "-r",
-                                                ctg + ":" + std::to_string(lo) + "-" + std::to_string(hi), "--min-MQ", "0", "--min-BQ", "0"};
-                if (!region_job) { cmd.push_back("-l"); cmd.push_back(j.bed_path); }      // the reference's order of options
-                cmd.push_back("--excl-flags");
-                cmd.push_back("2316");
-                if (cfg->samtools_max_depth > 0) { cmd.push_back("--max-depth"); cmd.push_back(std::to_string(cfg->samtools_max_depth)); }
-                cmd.push_back(j.bam_path);
-                std::vector<char> text;
-                if (!capture_stdout(cmd, &text, &err)) { fail(err); return false; }
-                int on_dev = 0;
-                if (cfg->device_tokenise && !text.empty()) rc = pack_from_text_device(s, text.data(), text.size(), stream, &on_dev);
-                if (rc == CTO_OK && on_dev) piled_on_device = true;
-                else if (rc == CTO_OK) {
-                    const size_t ecap = text.size() / 3 + 4096;
-                    if (s->stage.ensure(ecap * 4 + text.size() / 4 + (size_t(1) << 20)) != CTO_OK) { fail(cto_last_error()); return false; }
-                    rc = pack_from_mpileup_impl(text.empty() ? "" : text.data(), text.size(), s->ref.data(), s->ref_start, s->ref.size(),
-                                                cfg->max_indel_length, static_cast<uint32_t*>(s->stage.p), ecap, &s->pack);
-                }
-            } else {
-                InflateCtx* c = nullptr;
-                int done = 0;
-                // a device-inflate context is free: this chunk's blocks go to the GPU.  A REGION job waits for one: piled up at every
-                // position it is seven times a BED chunk's work, which the host reader needs most of a second of a core for
-                // A BED chunk does not wait (CTO_CTX_WAIT_MS, default 0): measured with 96 chunks, waiting 0 / 10 / 20 / 40 ms for a context
-                // sends 68 / 72 / 72 / 80 of them through the device and gives 667 / 654 / 646 / 612 k sites/s - for BED chunks the device
-                // is the busier side, the cores take what it cannot
-                static const int ctx_wait_ms = [] { const char* e = getenv("CTO_CTX_WAIT_MS"); return e ? atoi(e) : 0; }();
-                if (region_job && cfg->device_pileup && !inflate_ctx.empty() ? free_ctx.pop(&c)
-                                                                              : (inflate_ctx.empty() || ctx_wait_ms <= 0 ? free_ctx.try_pop(&c) : free_ctx.pop_for(&c, ctx_wait_ms))) {
-                    rc = pack_from_bam_device(j, ctg, lo, hi, iv, s, c, &done);
-                    free_ctx.push(c);
-                    piled_on_device = rc == CTO_OK && done == 2;
-                }
-                if (!done && rc == CTO_OK)
-                    rc = cto_pack_from_bam(j.bam_path, nullptr, ctg.c_str(), lo, hi, iv.empty() ? nullptr : iv.data(), int64_t(iv.size() / 2),
-                                           s->ref.data(), s->ref_start, s->ref.size(), 2316, 0, cfg->max_depth, cfg->max_indel_length, &s->pack);
-            }
+            if (!pack_from_alignments(s, j, ctg, region_job, lo, hi, iv, stream, &piled_on_device)) return false;
         }
-        if (rc != CTO_OK) { fail(cto_last_error()); return false; }
-        if (piled_on_device) {               // the pack is in the slot's device buffers already (pack_from_bam_device), s->uploaded recorded
-            { std::lock_guard<std::mutex> g(stat_m); pack_s += now_s() - t_pack; }
-            return region_job ? extract_sites(s, j, cand_lo, cand_hi, stream) : true;
+        if (piled_on_device) {               // the pack is in the slot's device buffers already (adopt_device_pack), s->uploaded recorded
+            std::lock_guard<std::mutex> g(stat_m);
+            st.pack_s += now_s() - t_pack;
+        } else {
+            if (cto_pack_view_of(s->pack, &s->hv) != CTO_OK) { fail(cto_last_error()); return false; }
+            const double t_up = now_s();
+            if (!upload(s, stream)) return false;
+            std::lock_guard<std::mutex> g(stat_m);
+            st.pack_s += t_up - t_pack;
+            st.upload_s += now_s() - t_up;
         }
-        if (cto_pack_view_of(s->pack, &s->hv) != CTO_OK) { fail(cto_last_error()); return false; }
-        // ---- upload ----
-        const double t_up = now_s();
-        // One copy per chunk out of a page-locked staging buffer.  (hipMemcpyAsync from the pack's pageable arrays goes through the
-        // runtime's own staging buffer, which every producer thread shares: measured, 8 producers spent 2.4 ms per chunk in those
-        // calls, 16 producers 6.6 ms, and the whole pipeline levelled off at ~8.5 GB/s of uploads = 1.4-1.6 M sites/s.)
+        return region_job ? extract_sites(s, j, cand_lo, cand_hi, stream) : true;
+    }
+
+    // One copy per chunk out of a page-locked staging buffer.  (hipMemcpyAsync from the pack's pageable arrays goes through the
+    // runtime's own staging buffer, which every producer thread shares: measured, 8 producers spent 2.4 ms per chunk in those
+    // calls, 16 producers 6.6 ms, and the whole pipeline levelled off at ~8.5 GB/s of uploads = 1.4-1.6 M sites/s.)
+    bool upload(Slot* s, hipStream_t stream) {
         const cto_pack_view& h = s->hv;
-        const size_t nc = size_t(h.n_cols), ne = size_t(h.n_entries), nk = size_t(h.n_keys), ns = s->sites.size();
-        const void* src[8] = {h.entries, h.col_pos, h.col_ref, h.col_off, h.key_off, h.key_meta, h.key_group, s->sites.data()};
-        const size_t bytes[8] = {ne * 4, nc * 4, nc, (nc + 1) * 8, (nc + 1) * 4, nk, nk * 4, ns * 4};
-        size_t off[8], total = 0;
-        for (int i = 0; i < 8; ++i) { off[i] = total; total += (bytes[i] + 255) / 256 * 256 + 256; }
-        const bool in_place = h.entries == s->stage.p && ne > 0;          // entries first: already there for the text producer
-        if (s->stage.grow_keeping(total, in_place ? bytes[0] : 0) != CTO_OK || s->pack_dev.ensure(total) != CTO_OK) { fail(cto_last_error()); return false; }
+        const PackLayout lay(h, s->sites.data(), s->sites.size());
+        const bool in_place = h.entries == s->stage.p && h.n_entries > 0;          // entries first: already there for the text producer
+        if (s->stage.grow_keeping(lay.total, in_place ? lay.bytes[0] : 0) != CTO_OK || s->pack_dev.ensure(lay.total) != CTO_OK) { fail(cto_last_error()); return false; }
         char* hs = static_cast<char*>(s->stage.p);
         if (in_place) {                      // grow_keeping may have moved the staging buffer: nothing may keep pointing at the old one
             s->pack->ext_entries = reinterpret_cast<uint32_t*>(hs);
             s->hv.entries = reinterpret_cast<const uint32_t*>(hs);
         }
-        for (int i = in_place ? 1 : 0; i < 8; ++i)
-            if (bytes[i]) memcpy(hs + off[i], src[i], bytes[i]);
-        if (hipMemcpyAsync(s->pack_dev.p, hs, total, hipMemcpyHostToDevice, stream) != hipSuccess) { fail("hipMemcpyAsync failed"); return false; }
-        const char* d = static_cast<const char*>(s->pack_dev.p);
+        for (int i = in_place ? 1 : 0; i < PackLayout::PARTS; ++i)
+            if (lay.bytes[i]) memcpy(hs + lay.off[i], lay.src[i], lay.bytes[i]);
+        if (hipMemcpyAsync(s->pack_dev.p, hs, lay.total, hipMemcpyHostToDevice, stream) != hipSuccess) { fail("hipMemcpyAsync failed"); return false; }
         s->dv = h;
-        s->dv.entries = reinterpret_cast<const uint32_t*>(d + off[0]);
-        s->dv.col_pos = reinterpret_cast<const int32_t*>(d + off[1]);
-        s->dv.col_ref = reinterpret_cast<const uint8_t*>(d + off[2]);
-        s->dv.col_off = reinterpret_cast<const int64_t*>(d + off[3]);
-        s->dv.key_off = reinterpret_cast<const int32_t*>(d + off[4]);
-        s->dv.key_meta = reinterpret_cast<const uint8_t*>(d + off[5]);
-        s->dv.key_group = reinterpret_cast<const int32_t*>(d + off[6]);
-        s->d_site_pos = reinterpret_cast<const int32_t*>(d + off[7]);
+        lay.bind(s->pack_dev.p, &s->dv, &s->d_site_pos);
         if (hipEventRecord(s->uploaded, stream) != hipSuccess) { fail("hipEventRecord failed"); return false; }
-        { std::lock_guard<std::mutex> g(stat_m); pack_s += t_up - t_pack; upload_s += now_s() - t_up; }
-        return region_job ? extract_sites(s, j, cand_lo, cand_hi, stream) : true;
+        return true;
     }
 
     // REGION job: STEP 1 of the reference on the pack that is now in HBM (the gates of extract_candidates_calling.py:55-169 as
@@ -787,8 +533,7 @@ struct Run {
         if (nc == 0) {
             if (j.candidates_path) { FILE* f = fopen(j.candidates_path, "w"); if (f) fclose(f); }
             if (j.hybrid_info_path) { FILE* f = fopen(j.hybrid_info_path, "w"); if (f) fclose(f); }
-            if (cfg->verbose) fprintf(stderr, "[INFO] %s total processed positions: 0\n", j.ctg_name);
-            return false;
+            return nothing_to_call(j);
         }
         const int64_t nb = cdiv(nc, 256);
         if (s->xflags.ensure(size_t(nc)) != CTO_OK || s->xdepth.ensure(size_t(nc) * 4) != CTO_OK ||
@@ -888,77 +633,97 @@ struct Run {
             for (int64_t i = 0; i < n; ++i) fprintf(f, "%s\t%d\t%d\n", j.ctg_name, std::max(h[i] - 17, 1), h[i] + 17);
             if (fclose(f) != 0) { fail(std::string("short write to ") + j.candidates_path); return false; }
         }
-        { std::lock_guard<std::mutex> g(stat_m); pack_s += now_s() - t0; }
-        if (n == 0) {
-            if (cfg->verbose) fprintf(stderr, "[INFO] %s total processed positions: 0\n", j.ctg_name);
-            return false;
-        }
-        return true;
+        { std::lock_guard<std::mutex> g(stat_m); st.pack_s += now_s() - t0; }
+        return n > 0 || nothing_to_call(j);
     }
 
-    // Tensor creation of one chunk on `main`: the [33][34] inputs of both networks and what the writers need of the candidate columns.
+    // Tensor creation of one chunk on `main`: the [33][34] inputs of both networks (rows of x_aff / x_neg) and what the writers need of
+    // the candidate columns (into the chunk's result buffer).
     // One kernel (a workgroup per candidate, the column histograms never leave LDS); CTO_FUSED_FEATURIZE=0 selects the two-stage path
     // through the per-column vectors in HBM (kept for A/B runs - same results).
     bool fused_featurize = true;
-    int tensors(Slot* s, int64_t n, float* x_aff, float* x_neg, int32_t* site_info, int16_t* site_colvec, int32_t* sitefirst, uint32_t* keycnt,
-                int32_t* keyfirst, hipStream_t main) {
+    int tensors(Slot* s, int64_t n, float* x_aff, float* x_neg, hipStream_t main) {
         int rc;
+        void* rd = s->res_dev.p;
+        int32_t* site_info = s->res.site_info(rd);
         // heavily overlapping windows (candidates a few bases apart) share most of their columns: the one-kernel path would histogram
         // them once per candidate, the two-stage path once (measured equal at ~8 columns per candidate; same results either way)
         if (fused_featurize && s->hv.n_cols >= 8 * n)
-            return cto_featurize_sites(&s->dv, s->d_site_pos, n, cfg->min_bq, cfg->min_rescale_cov, x_aff, x_neg, nullptr, nullptr, site_info, site_colvec,
-                                       sitefirst, keycnt, keyfirst, main);
+            return cto_featurize_sites(&s->dv, s->d_site_pos, n, cfg->min_bq, cfg->min_rescale_cov, x_aff, x_neg, nullptr, nullptr, site_info, s->res.colvec(rd),
+                                       s->res.sitefirst(rd), s->res.keycnt(rd), s->res.keyfirst(rd), main);
         const size_t nc = size_t(std::max<int64_t>(s->hv.n_cols, 1));
         if ((rc = s->colvec.ensure(nc * CTO_COLVEC_STRIDE * 2)) || (rc = s->coldepth.ensure(nc * 8))) return rc;
         auto* colvec = static_cast<int16_t*>(s->colvec.p);
-        if ((rc = cto_featurize_columns(&s->dv, cfg->min_bq, colvec, static_cast<int32_t*>(s->coldepth.p), keycnt, main))) return rc;
+        if ((rc = cto_featurize_columns(&s->dv, cfg->min_bq, colvec, static_cast<int32_t*>(s->coldepth.p), s->res.keycnt(rd), main))) return rc;
         if ((rc = cto_gather_windows(&s->dv, colvec, static_cast<int32_t*>(s->coldepth.p), s->d_site_pos, n, cfg->min_bq, cfg->min_rescale_cov, x_aff,
-                                     x_neg, nullptr, nullptr, site_info, sitefirst, keyfirst, main)))
+                                     x_neg, nullptr, nullptr, site_info, s->res.sitefirst(rd), s->res.keyfirst(rd), main)))
             return rc;
-        hipLaunchKernelGGL(k_gather_rows, dim3(unsigned(n)), dim3(128), 0, main, colvec, site_info, n, site_colvec);
+        hipLaunchKernelGGL(k_gather_rows, dim3(unsigned(n)), dim3(128), 0, main, colvec, site_info, n, s->res.colvec(rd));
         CTO_HIP(hipGetLastError());
         return CTO_OK;
     }
 
-    int launch(Slot* s, hipStream_t main, hipStream_t copy_back, cto_model* aff, cto_model* neg) {
-        const int K = cfg->K;
+    static constexpr size_t X_ROW = size_t(CTO_NPOS) * CTO_NCHAN;      // floats of one site's network input
+
+    // What both launch modes begin a chunk with: its result layout and buffers, the wait for its upload, `begin`, tensor creation on `main`.
+    // `carried` rows of earlier chunks (tile stream only) move to the front of the chunk's input buffers first, its own rows follow them.
+    int begin_chunk(Slot* s, int64_t carried, hipStream_t main) {
         const int64_t n = int64_t(s->sites.size());
-        const size_t nk = size_t(std::max<int64_t>(s->hv.n_keys, 1));
+        const size_t row = X_ROW * 4;
         int rc;
         // everything the writers need goes into ONE device buffer and comes back with ONE copy on the copy-back stream: seven copies
         // queued behind the kernels on the launch stream cost ~0.1 ms per chunk in which the next chunk's kernels could not start
-        const size_t rbytes[7] = {size_t(n) * 48, size_t(n) * CTO_COLVEC_STRIDE * 2, size_t(n) * 32, size_t(n) * 16, size_t(n) * 8, nk * 4, nk * 8};
-        size_t total = 0;
-        for (int i = 0; i < 7; ++i) { s->roff[i] = total; total += (rbytes[i] + 255) / 256 * 256; }
-        if ((rc = s->x_aff.ensure(size_t(n) * CTO_NPOS * CTO_NCHAN * 4)) || (rc = s->x_neg.ensure(size_t(n) * CTO_NPOS * CTO_NCHAN * 4)) ||
-            (rc = s->la.ensure(size_t(K) * n * 8)) || (rc = s->ln.ensure(size_t(K) * n * 8)) || (rc = s->post.ensure(size_t(n) * K * 8)) ||
-            (rc = s->res_dev.ensure(total)) || (rc = s->res_host.ensure(total)))
+        s->res = ResultLayout(n, s->hv.n_keys);
+        if ((rc = s->x_aff.ensure(size_t(carried + n) * row)) || (rc = s->x_neg.ensure(size_t(carried + n) * row)) ||
+            (rc = s->res_dev.ensure(s->res.total)) || (rc = s->res_host.ensure(s->res.total)))
             return rc;
-        char* rd = static_cast<char*>(s->res_dev.p);
-        auto* site_info = reinterpret_cast<int32_t*>(rd + s->roff[0]);
-        auto* site_colvec = reinterpret_cast<int16_t*>(rd + s->roff[1]);
-        auto* sitefirst = reinterpret_cast<int32_t*>(rd + s->roff[2]);
-        auto* decision = reinterpret_cast<int32_t*>(rd + s->roff[3]);
-        auto* qual = reinterpret_cast<double*>(rd + s->roff[4]);
-        auto* keycnt = reinterpret_cast<uint32_t*>(rd + s->roff[5]);
-        auto* keyfirst = reinterpret_cast<int32_t*>(rd + s->roff[6]);
         CTO_HIP(hipStreamWaitEvent(main, s->uploaded, 0));
         CTO_HIP(hipEventRecord(s->begin, main));
-        if ((rc = tensors(s, n, static_cast<float*>(s->x_aff.p), static_cast<float*>(s->x_neg.p), site_info, site_colvec, sitefirst, keycnt, keyfirst,
-                          main)))
-            return rc;
-        const float* x_neg = cfg->neg_reads_aff ? static_cast<const float*>(s->x_aff.p) : static_cast<const float*>(s->x_neg.p);
-        if ((rc = cto_model_forward(neg, x_neg, n, static_cast<float*>(s->ln.p), main))) return rc;
-        if ((rc = cto_model_forward(aff, static_cast<const float*>(s->x_aff.p), n, static_cast<float*>(s->la.p), main))) return rc;
-        if ((rc = cto_posterior(static_cast<const float*>(s->la.p), static_cast<const float*>(s->ln.p), K, n, cfg->d_lik, cfg->d_edges, nullptr,
-                                static_cast<double*>(s->post.p), decision, qual, main)))
-            return rc;
-        CTO_HIP(hipEventRecord(s->kernels_end, main));
+        if (carried > 0) {
+            CTO_HIP(hipMemcpyAsync(s->x_aff.p, static_cast<char*>(carry_home->x_aff.p) + size_t(carry_at) * row, size_t(carried) * row, hipMemcpyDeviceToDevice, main));
+            if (!cfg->neg_reads_aff)
+                CTO_HIP(hipMemcpyAsync(s->x_neg.p, static_cast<char*>(carry_home->x_neg.p) + size_t(carry_at) * row, size_t(carried) * row, hipMemcpyDeviceToDevice, main));
+        }
+        return tensors(s, n, static_cast<float*>(s->x_aff.p) + size_t(carried) * X_ROW, static_cast<float*>(s->x_neg.p) + size_t(carried) * X_ROW, main);
+    }
+
+    // room for the logits and posteriors of `m` rows (growing frees, and a free waits for the device: before a chunk queues anything)
+    int grow_outputs(Slot* home, int64_t m) {
+        const size_t b = size_t(cfg->K) * size_t(m) * 8;
+        int rc;
+        return (rc = home->la.ensure(b)) || (rc = home->ln.ensure(b)) ? rc : home->post.ensure(b);
+    }
+
+    // both networks and the epilogue over `m` rows of inputs on `main`; logits and posteriors stay in `home`'s buffers
+    int networks(Slot* home, const float* x_aff, const float* x_neg, int64_t m, int32_t* decision, double* qual, hipStream_t main, cto_model* aff,
+                 cto_model* neg) {
+        const int K = cfg->K;
+        int rc;
+        if ((rc = cto_model_forward(neg, cfg->neg_reads_aff ? x_aff : x_neg, m, static_cast<float*>(home->ln.p), main))) return rc;
+        if ((rc = cto_model_forward(aff, x_aff, m, static_cast<float*>(home->la.p), main))) return rc;
+        return cto_posterior(static_cast<const float*>(home->la.p), static_cast<const float*>(home->ln.p), K, m, cfg->d_lik, cfg->d_edges, nullptr,
+                             static_cast<double*>(home->post.p), decision, qual, main);
+    }
+
+    // the chunk's results, complete on `main`, go to the host on the copy-back stream; s->done follows them
+    int send_back(Slot* s, hipStream_t main, hipStream_t copy_back) {
         CTO_HIP(hipEventRecord(s->computed, main));
         CTO_HIP(hipStreamWaitEvent(copy_back, s->computed, 0));
-        CTO_HIP(hipMemcpyAsync(s->res_host.p, s->res_dev.p, total, hipMemcpyDeviceToHost, copy_back));
+        CTO_HIP(hipMemcpyAsync(s->res_host.p, s->res_dev.p, s->res.total, hipMemcpyDeviceToHost, copy_back));
         CTO_HIP(hipEventRecord(s->done, copy_back));
         return CTO_OK;
+    }
+
+    // a chunk as a launch of its own: decision and QUAL are written straight into its result buffer
+    int launch(Slot* s, hipStream_t main, hipStream_t copy_back, cto_model* aff, cto_model* neg) {
+        const int64_t n = int64_t(s->sites.size());
+        int rc;
+        if ((rc = grow_outputs(s, n)) || (rc = begin_chunk(s, 0, main))) return rc;
+        void* rd = s->res_dev.p;
+        if ((rc = networks(s, static_cast<const float*>(s->x_aff.p), static_cast<const float*>(s->x_neg.p), n, s->res.decision(rd), s->res.qual(rd), main, aff, neg)))
+            return rc;
+        CTO_HIP(hipEventRecord(s->kernels_end, main));
+        return send_back(s, main, copy_back);
     }
 
     // ---- the networks fed by a STREAM of sites instead of by chunks --------------------------------------------------------------
@@ -975,7 +740,7 @@ struct Run {
     int64_t carry_at = 0;                    // ... starting at this row
     int64_t round_sites = 4096;
     size_t max_pending = 2;
-    hipEvent_t flush_begin = nullptr, flush_end = nullptr;
+    Event flush_begin, flush_end;            // created for a tile stream only
     bool flush_timed = false;
 
     int64_t pending_rows() const { int64_t c = 0; for (const Pending& q : pending) c += q.cnt; return c; }
@@ -983,18 +748,11 @@ struct Run {
     // networks + epilogue over rows [at, at + m) of `home`'s input buffers; results dealt out to the first m pending rows
     int run_networks(Slot* home, int64_t at, int64_t m, hipStream_t main, hipStream_t copy_back, cto_model* aff, cto_model* neg,
                      std::vector<Slot*>* complete, hipEvent_t kernels_end) {
-        const int K = cfg->K;
+        constexpr size_t DEC = ResultLayout::DECISION_ROW, QUAL = ResultLayout::QUAL_ROW;
         int rc;
-        const size_t row = size_t(CTO_NPOS) * CTO_NCHAN;
-        if ((rc = home->la.ensure(size_t(K) * m * 8)) || (rc = home->ln.ensure(size_t(K) * m * 8)) || (rc = home->post.ensure(size_t(m) * K * 8)) ||
-            (rc = home->dec_l.ensure(size_t(m) * 16)) || (rc = home->qual_l.ensure(size_t(m) * 8)))
-            return rc;
-        const float* xa = static_cast<const float*>(home->x_aff.p) + size_t(at) * row;
-        const float* xn = cfg->neg_reads_aff ? xa : static_cast<const float*>(home->x_neg.p) + size_t(at) * row;
-        if ((rc = cto_model_forward(neg, xn, m, static_cast<float*>(home->ln.p), main))) return rc;
-        if ((rc = cto_model_forward(aff, xa, m, static_cast<float*>(home->la.p), main))) return rc;
-        if ((rc = cto_posterior(static_cast<const float*>(home->la.p), static_cast<const float*>(home->ln.p), K, m, cfg->d_lik, cfg->d_edges, nullptr,
-                                static_cast<double*>(home->post.p), static_cast<int32_t*>(home->dec_l.p), static_cast<double*>(home->qual_l.p), main)))
+        if ((rc = grow_outputs(home, m)) || (rc = home->dec_l.ensure(size_t(m) * DEC)) || (rc = home->qual_l.ensure(size_t(m) * QUAL))) return rc;
+        if ((rc = networks(home, static_cast<const float*>(home->x_aff.p) + size_t(at) * X_ROW, static_cast<const float*>(home->x_neg.p) + size_t(at) * X_ROW, m,
+                           static_cast<int32_t*>(home->dec_l.p), static_cast<double*>(home->qual_l.p), main, aff, neg)))
             return rc;
         if (kernels_end) CTO_HIP(hipEventRecord(kernels_end, main));   // before any chunk of this launch can reach a writer, which reads it
         int64_t o = 0;
@@ -1008,19 +766,16 @@ struct Run {
         for (Pending& q : pending) {
             if (o >= m) break;
             const int64_t take = std::min(q.cnt, m - o);
-            char* rd = static_cast<char*>(q.s->res_dev.p);
-            CTO_HIP(hipMemcpyAsync(rd + q.s->roff[3] + size_t(q.row0) * 16, static_cast<char*>(home->dec_l.p) + size_t(o) * 16, size_t(take) * 16,
-                                   hipMemcpyDeviceToDevice, main));
-            CTO_HIP(hipMemcpyAsync(rd + q.s->roff[4] + size_t(q.row0) * 8, static_cast<char*>(home->qual_l.p) + size_t(o) * 8, size_t(take) * 8,
-                                   hipMemcpyDeviceToDevice, main));
+            void* rd = q.s->res_dev.p;
+            CTO_HIP(hipMemcpyAsync(reinterpret_cast<char*>(q.s->res.decision(rd)) + size_t(q.row0) * DEC, static_cast<char*>(home->dec_l.p) + size_t(o) * DEC,
+                                   size_t(take) * DEC, hipMemcpyDeviceToDevice, main));
+            CTO_HIP(hipMemcpyAsync(reinterpret_cast<char*>(q.s->res.qual(rd)) + size_t(q.row0) * QUAL, static_cast<char*>(home->qual_l.p) + size_t(o) * QUAL,
+                                   size_t(take) * QUAL, hipMemcpyDeviceToDevice, main));
             q.row0 += take;
             q.cnt -= take;
             o += take;
             if (q.cnt == 0) {
-                CTO_HIP(hipEventRecord(q.s->computed, main));
-                CTO_HIP(hipStreamWaitEvent(copy_back, q.s->computed, 0));
-                CTO_HIP(hipMemcpyAsync(q.s->res_host.p, q.s->res_dev.p, q.s->res_total, hipMemcpyDeviceToHost, copy_back));
-                CTO_HIP(hipEventRecord(q.s->done, copy_back));
+                if ((rc = send_back(q.s, main, copy_back))) return rc;
                 complete->push_back(q.s);
                 ++used;
             }
@@ -1031,33 +786,8 @@ struct Run {
     // one chunk into the stream; chunks whose last row came back go to *complete (in chunk order)
     int launch_stream(Slot* s, hipStream_t main, hipStream_t copy_back, cto_model* aff, cto_model* neg, std::vector<Slot*>* complete) {
         const int64_t n = int64_t(s->sites.size()), c = pending_rows();
-        const size_t nk = size_t(std::max<int64_t>(s->hv.n_keys, 1));
-        const size_t row = size_t(CTO_NPOS) * CTO_NCHAN * 4;
         int rc;
-        const size_t rbytes[7] = {size_t(n) * 48, size_t(n) * CTO_COLVEC_STRIDE * 2, size_t(n) * 32, size_t(n) * 16, size_t(n) * 8, nk * 4, nk * 8};
-        size_t total = 0;
-        for (int i = 0; i < 7; ++i) { s->roff[i] = total; total += (rbytes[i] + 255) / 256 * 256; }
-        s->res_total = total;
-        if ((rc = s->x_aff.ensure(size_t(c + n) * row)) || (rc = s->x_neg.ensure(size_t(c + n) * row)) ||
-            (rc = s->res_dev.ensure(total)) || (rc = s->res_host.ensure(total)))
-            return rc;
-        char* rd = static_cast<char*>(s->res_dev.p);
-        auto* site_info = reinterpret_cast<int32_t*>(rd + s->roff[0]);
-        auto* site_colvec = reinterpret_cast<int16_t*>(rd + s->roff[1]);
-        auto* sitefirst = reinterpret_cast<int32_t*>(rd + s->roff[2]);
-        auto* keycnt = reinterpret_cast<uint32_t*>(rd + s->roff[5]);
-        auto* keyfirst = reinterpret_cast<int32_t*>(rd + s->roff[6]);
-        CTO_HIP(hipStreamWaitEvent(main, s->uploaded, 0));
-        CTO_HIP(hipEventRecord(s->begin, main));
-        if (c > 0) {                         // the rows still waiting move to the front of this chunk's input buffers
-            CTO_HIP(hipMemcpyAsync(s->x_aff.p, static_cast<char*>(carry_home->x_aff.p) + size_t(carry_at) * row, size_t(c) * row, hipMemcpyDeviceToDevice, main));
-            if (!cfg->neg_reads_aff)
-                CTO_HIP(hipMemcpyAsync(s->x_neg.p, static_cast<char*>(carry_home->x_neg.p) + size_t(carry_at) * row, size_t(c) * row, hipMemcpyDeviceToDevice, main));
-        }
-        if ((rc = tensors(s, n, reinterpret_cast<float*>(static_cast<char*>(s->x_aff.p) + size_t(c) * row),
-                          reinterpret_cast<float*>(static_cast<char*>(s->x_neg.p) + size_t(c) * row), site_info, site_colvec, sitefirst, keycnt, keyfirst,
-                          main)))
-            return rc;
+        if ((rc = begin_chunk(s, c, main))) return rc;       // the rows still waiting move to the front of this chunk's input buffers
         pending.push_back({s, 0, n});
         carry_home = s;
         carry_at = 0;
@@ -1076,9 +806,9 @@ struct Run {
     int flush_stream(hipStream_t main, hipStream_t copy_back, cto_model* aff, cto_model* neg, std::vector<Slot*>* complete) {
         const int64_t c = pending_rows();
         if (c == 0) { for (const Pending& q : pending) complete->push_back(q.s); pending.clear(); return CTO_OK; }
-        if (flush_begin) CTO_HIP(hipEventRecord(flush_begin, main));
+        if (flush_begin.e) CTO_HIP(hipEventRecord(flush_begin, main));
         const int rc = run_networks(carry_home, carry_at, c, main, copy_back, aff, neg, complete, flush_end);
-        if (rc == CTO_OK && flush_end) flush_timed = true;
+        if (rc == CTO_OK && flush_end.e) flush_timed = true;
         return rc;
     }
 
@@ -1089,24 +819,21 @@ struct Run {
         {
             float ms = 0;
             // the kernels this chunk's launch queued (with a tile stream, its own tail runs - and is counted - in the next chunk's launch)
-            if (hipEventElapsedTime(&ms, s->begin, s->kernels_end) == hipSuccess) { std::lock_guard<std::mutex> g(stat_m); device_s += ms * 1e-3; }
+            if (hipEventElapsedTime(&ms, s->begin, s->kernels_end) == hipSuccess) { std::lock_guard<std::mutex> g(stat_m); st.device_s += ms * 1e-3; }
         }
         const int64_t n = int64_t(s->sites.size());
-        char* rh = static_cast<char*>(s->res_host.p);
-        auto* info = reinterpret_cast<int32_t*>(rh + s->roff[0]);
-        const auto* h_site_colvec = reinterpret_cast<const int16_t*>(rh + s->roff[1]);
-        const auto* h_sitefirst = reinterpret_cast<const int32_t*>(rh + s->roff[2]);
-        const auto* h_decision = reinterpret_cast<const int32_t*>(rh + s->roff[3]);
-        const auto* h_qual = reinterpret_cast<const double*>(rh + s->roff[4]);
+        void* rh = s->res_host.p;
+        int32_t* info = s->res.site_info(rh);
+        const int32_t* h_decision = s->res.decision(rh);
         static const uint32_t zero_k[1] = {0};
         static const int32_t zero_kf[2] = {0, 0};
-        const uint32_t* keycnt = s->hv.n_keys ? reinterpret_cast<const uint32_t*>(rh + s->roff[5]) : zero_k;
-        const int32_t* keyfirst = s->hv.n_keys ? reinterpret_cast<const int32_t*>(rh + s->roff[6]) : zero_kf;
+        const uint32_t* keycnt = s->hv.n_keys ? s->res.keycnt(rh) : zero_k;
+        const int32_t* keyfirst = s->hv.n_keys ? s->res.keyfirst(rh) : zero_kf;
         std::vector<int64_t> alt_off(size_t(n) + 1, 0);
         std::vector<char> alt(size_t(256 * n + (1 << 16)));
         int64_t used = -1;
         for (int tries = 0; tries < 8; ++tries) {
-            used = cto_alt_info_batch_sites(s->pack, n, info, 0, h_site_colvec, h_sitefirst,
+            used = cto_alt_info_batch_sites(s->pack, n, info, 0, s->res.colvec(rh), s->res.sitefirst(rh),
                                             keycnt, keyfirst, alt.data(), alt.size(), alt_off.data());
             if (used >= 0) break;
             if (!strstr(cto_last_error(), "buffer too small")) break;
@@ -1125,7 +852,7 @@ struct Run {
         int64_t tu = -1;
         for (int tries = 0; tries < 6; ++tries) {
             tu = cto_vcf_rows_batch(j.ctg_name, n, s->sites.data(), centre.data(), alt.data(), alt_off.data(), info, h_decision,
-                                    h_qual, cfg->K, cfg->show_ref, cfg->qual_pass, text.data(), text.size(), counts);
+                                    s->res.qual(rh), cfg->K, cfg->show_ref, cfg->qual_pass, text.data(), text.size(), counts);
             if (tu != CTO_ENOMEM) break;
             text.resize(text.size() * 4);
         }
@@ -1157,11 +884,108 @@ struct Run {
         clamped += counts[3];
         return true;
     }
+
+    // ---- the three kinds of thread -------------------------------------------------------------------------------------------------
+    // a producer: chunks from the job list into free slots, on `shared` (a copy stream of several producers) or a stream of its own
+    void producer(int dev, hipStream_t shared) {
+        Stream own;
+        hipStream_t copy = shared;
+        tl_pack_threads = cfg->pack_threads;                     // the tokeniser's / BAM decoder's own threads per call
+        if (shared) (void)hipSetDevice(dev);
+        else if (hipSetDevice(dev) != hipSuccess || own.create() != CTO_OK) fail("producer: no HIP stream");
+        else copy = own;
+        for (;;) {
+            if (failed) break;
+            const int64_t j = next_job.fetch_add(1);
+            if (j >= n_jobs) break;
+            Slot* s = nullptr;
+            if (!free_slots.pop(&s)) break;
+            if (failed) {                                        // the run failed while this thread waited for a slot: what the slot's
+                free_slots.push(s);                              // last chunk queued on the device may still be running - leave it alone
+                break;
+            }
+            s->job = j;
+            const double t0 = now_s();
+            bool ok = false;
+            try {
+                ok = copy && produce(s, copy);
+            } catch (const std::exception& e) {                  // bad_alloc on a huge chunk: an error of the run, not of the process
+                fail(std::string("producer: ") + e.what());
+            }
+            { std::lock_guard<std::mutex> g(stat_m); st.produce_s += now_s() - t0; }
+            if (ok) to_launch.push(s);
+            else free_slots.push(s);                             // nothing to call here (or an error: `failed` is set)
+        }
+        if (copy) (void)hipStreamSynchronize(copy);
+    }
+
+    void writer(int dev) {
+        (void)hipSetDevice(dev);
+        Slot* s = nullptr;
+        while (to_write.pop(&s)) {
+            const double t0 = now_s();
+            try {
+                if (!failed) finish(s);
+            } catch (const std::exception& e) {
+                fail(std::string("writer: ") + e.what());
+            }
+            { std::lock_guard<std::mutex> g(stat_m); st.finish_s += now_s() - t0; }
+            free_slots.push(s);
+        }
+    }
+
+    // the launcher (the calling thread): every chunk the producers deliver goes to the device - as a launch of its own, on `main` and
+    // `second` in turn, or into the tile stream on `main` - and from there to the writers; returns when the producers are done
+    int launcher(hipStream_t main, hipStream_t second, hipStream_t copy_back, bool tile_stream) {
+        int rc = CTO_OK;
+        int64_t launched = 0;
+        std::vector<Slot*> complete;
+        auto hand_over = [&] { for (Slot* c : complete) (failed ? free_slots : to_write).push(c); complete.clear(); };
+        auto abandon_pending = [&] {             // a failed run: the chunks still waiting for rows give their slots back
+            if (!pending.empty()) (void)hipStreamSynchronize(main);
+            for (const Pending& q : pending) free_slots.push(q.s);
+            pending.clear();
+        };
+        for (;;) {
+            Slot* s = nullptr;
+            const double t0 = now_s();
+            if (!to_launch.pop(&s)) break;
+            const double t1 = now_s();
+            st.launcher_wait_s += t1 - t0;
+            bool queued = false;
+            if (!failed) {
+                int r;
+                if (tile_stream) {
+                    r = launch_stream(s, main, copy_back, cfg->aff, cfg->neg, &complete);
+                    queued = r == CTO_OK || std::any_of(pending.begin(), pending.end(), [s](const Pending& q) { return q.s == s; });
+                } else {
+                    const bool odd = second && (launched++ & 1);
+                    r = launch(s, odd ? second : main, copy_back, odd ? cfg->aff2 : cfg->aff, odd ? cfg->neg2 : cfg->neg);
+                    if (r == CTO_OK) { complete.push_back(s); queued = true; }
+                }
+                if (r != CTO_OK) { fail(cto_last_error()); rc = r; }
+            }
+            st.launch_s += now_s() - t1;
+            if (!queued) {
+                (void)hipStreamSynchronize(main);                         // its buffers may be in use by what was queued before the failure
+                free_slots.push(s);
+            }
+            hand_over();
+            if (failed) abandon_pending();
+        }
+        if (tile_stream && !failed) {
+            const double t1 = now_s();
+            const int r = flush_stream(main, copy_back, cfg->aff, cfg->neg, &complete);
+            if (r != CTO_OK) { fail(cto_last_error()); rc = r; }
+            st.launch_s += now_s() - t1;
+            hand_over();
+        }
+        if (failed) abandon_pending();
+        return rc;
+    }
 };
 
-}  // namespace
-
-static int run_chunks(const cto_run_cfg* cfg, const cto_chunk_job* jobs, int64_t n_jobs, void* stream, cto_run_stats* stats) {
+int check_arguments(const cto_run_cfg* cfg, const cto_chunk_job* jobs, int64_t n_jobs) {
     CTO_REQUIRE(cfg && (jobs || n_jobs == 0) && cfg->aff && cfg->neg && cfg->d_lik && cfg->d_edges && cfg->ref_fa && cfg->vcf_header, CTO_EINVAL,
                 "cto_run_chunks: null argument");
     CTO_REQUIRE(cfg->K == 4 || cfg->K == 6, CTO_EINVAL, "cto_run_chunks: K must be 4 or 6");
@@ -1169,101 +993,70 @@ static int run_chunks(const cto_run_cfg* cfg, const cto_chunk_job* jobs, int64_t
         CTO_REQUIRE(jobs[i].ctg_name && jobs[i].vcf_path && (jobs[i].mpileup_path || jobs[i].bam_path) &&
                         (jobs[i].bed_path || (jobs[i].region_start >= 0 && jobs[i].region_end >= std::max<int64_t>(jobs[i].region_start, 1))),   // a first chunk of --chunk_id starts at 0 (:262)
                     CTO_EINVAL, "cto_run_chunks: job %lld is incomplete", (long long)i);
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (n_jobs == 0) return CTO_OK;
-    const int producers = std::max(1, cfg->producers), writers = std::max(1, cfg->writers);
-    const int depth = cfg->depth > 0 ? cfg->depth : producers + writers + 2;
-    Run run;
-    run.cfg = cfg;
-    run.jobs = jobs;
-    run.n_jobs = n_jobs;
-    {
-        std::string err;
-        CTO_REQUIRE(run.fasta.open(cfg->ref_fa, &err), CTO_EINVAL, "cto_run_chunks: %s", err.c_str());
-        CTO_REQUIRE(run.load_indel_regions(&err), CTO_EINVAL, "cto_run_chunks: %s", err.c_str());
-    }
-    int dev = 0;
-    CTO_HIP(hipGetDevice(&dev));
-    // slots (device + page-locked buffers, events) outlive the call: allocating and freeing ~100 MB of them per slot costs tens of
-    // milliseconds, which a short chunk list would pay on every call; cto_run_release() frees them
-    SlotReturn slots_back{&run.slots};
-    {
-        std::lock_guard<std::mutex> g(slot_cache_m());
-        auto& cache = slot_cache();
-        for (size_t i = 0; i < cache.size() && int(run.slots.size()) < depth;)
-            if (cache[i]->device == dev) {
-                run.slots.push_back(std::move(cache[i]));
-                cache.erase(cache.begin() + long(i));
-            } else {
-                ++i;
-            }
-    }
+    return CTO_OK;
+}
+
+// `depth` slots of device `dev` for the run: from the cache, the rest new
+int lease_slots(Run& run, Lease<Slot>& lease, int dev, int depth) {
+    lease.take(depth, [dev](const Slot& s) { return s.device == dev; });
     while (int(run.slots.size()) < depth) {
         run.slots.emplace_back(new Slot());
-        run.slots.back()->device = dev;
-        CTO_HIP(hipEventCreateWithFlags(&run.slots.back()->uploaded, hipEventDisableTiming));
-        CTO_HIP(hipEventCreate(&run.slots.back()->begin));
-        CTO_HIP(hipEventCreateWithFlags(&run.slots.back()->computed, hipEventDisableTiming));
-        CTO_HIP(hipEventCreate(&run.slots.back()->kernels_end));
-        CTO_HIP(hipEventCreateWithFlags(&run.slots.back()->done, hipEventBlockingSync));      // writers sleep, not spin, until their chunk is back
+        if (const int rc = run.slots.back()->open(dev)) return rc;
     }
     for (auto& sl : run.slots) run.free_slots.push(sl.get());
-    // device-inflate contexts (BAM jobs only), kept across calls like the slots
-    CtxReturn ctx_back{&run.inflate_ctx};
+    return CTO_OK;
+}
+
+// device-inflate contexts (BAM jobs only), kept across calls like the slots
+void lease_inflate_contexts(Run& run, Lease<InflateCtx>& lease, int dev) {
+    const cto_run_cfg* cfg = run.cfg;
     bool any_bam = false;
-    for (int64_t i = 0; i < n_jobs; ++i) any_bam = any_bam || !jobs[i].mpileup_path;
-    if (any_bam && cfg->inflate_cus > 0 && cfg->inflate_jobs > 0) {
-        int n_cu = 256;
-        (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
-        const int cus = std::max(8, std::min(cfg->inflate_cus, n_cu * 3 / 4));      // the networks keep at least a quarter of the chip
-        {
-            std::lock_guard<std::mutex> g(slot_cache_m());
-            auto& cache = inflate_cache();
-            for (size_t i = 0; i < cache.size() && int(run.inflate_ctx.size()) < cfg->inflate_jobs;)
-                if (cache[i]->device == dev && cache[i]->cus == cus) {
-                    run.inflate_ctx.push_back(std::move(cache[i]));
-                    cache.erase(cache.begin() + long(i));
-                } else {
-                    ++i;
-                }
+    for (int64_t i = 0; i < run.n_jobs; ++i) any_bam = any_bam || !run.jobs[i].mpileup_path;
+    if (!any_bam || cfg->inflate_cus <= 0 || cfg->inflate_jobs <= 0) return;
+    int n_cu = 256;
+    (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
+    const int cus = std::max(8, std::min(cfg->inflate_cus, n_cu * 3 / 4));      // the networks keep at least a quarter of the chip
+    lease.take(cfg->inflate_jobs, [dev, cus](const InflateCtx& c) { return c.device == dev && c.cus == cus; });
+    while (int(run.inflate_ctx.size()) < cfg->inflate_jobs) {
+        run.inflate_ctx.emplace_back(new InflateCtx());
+        if (run.inflate_ctx.back()->open(dev, cus) != CTO_OK) {           // no CU-masked streams on this runtime: host inflate only
+            if (cfg->verbose) fprintf(stderr, "[WARNING] device inflate disabled: %s\n", cto_last_error());
+            run.inflate_ctx.clear();
+            break;
         }
-        while (int(run.inflate_ctx.size()) < cfg->inflate_jobs) {
-            run.inflate_ctx.emplace_back(new InflateCtx());
-            if (run.inflate_ctx.back()->open(dev, cus) != CTO_OK) {           // no CU-masked streams on this runtime: host inflate only
-                if (cfg->verbose) fprintf(stderr, "[WARNING] device inflate disabled: %s\n", cto_last_error());
-                run.inflate_ctx.clear();
-                break;
-            }
+    }
+    for (auto& c : run.inflate_ctx) run.free_ctx.push(c.get());
+}
+
+// The streams of one call, declared before the threads that queue on them: they go (Stream drains, then destroys) after those are
+// joined, on every way out of run_chunks()
+struct RunStreams {
+    Stream own_main, copy_back, second;
+    std::vector<Stream> copy;                // the producers' shared copy streams
+    hipStream_t main = nullptr;
+    // `stream` waits for what is queued on `on` so far
+    static int order_behind(hipStream_t stream, hipStream_t on) {
+        Event before;
+        if (const int rc = before.create(hipEventDisableTiming)) return rc;
+        CTO_HIP(hipEventRecord(before, on));
+        CTO_HIP(hipStreamWaitEvent(stream, before, 0));
+        return CTO_OK;
+    }
+    int open(const cto_run_cfg* cfg, hipStream_t callers) {
+        int rc;
+        main = callers;
+        if (!main) {
+            // The legacy default stream synchronises with every blocking stream - the CU-masked inflate streams are such - and the networks
+            // and the inflate launches would exclude each other in time (measured: BAM -> VCF 350 k instead of 400-490 k sites/s).  The
+            // kernels get a non-blocking stream of this call, ordered behind what the caller has queued on the default stream so far.
+            if ((rc = own_main.create()) || (rc = order_behind(own_main, nullptr))) return rc;
+            main = own_main;
         }
-        for (auto& c : run.inflate_ctx) run.free_ctx.push(c.get());
+        if ((rc = copy_back.create())) return rc;
+        // a second compute stream for every other chunk, when the caller brought a second pair of handles (cto_run_cfg.aff2)
+        if (cfg->aff2 && cfg->neg2 && ((rc = second.create()) || (rc = order_behind(second, main)))) return rc;
+        return CTO_OK;
     }
-    hipStream_t main = static_cast<hipStream_t>(stream), own_main = nullptr;
-    if (!main) {
-        // The legacy default stream synchronises with every blocking stream - the CU-masked inflate streams are such - and the networks
-        // and the inflate launches would exclude each other in time (measured: BAM -> VCF 350 k instead of 400-490 k sites/s).  The
-        // kernels get a non-blocking stream of this call, ordered behind what the caller has queued on the default stream so far.
-        hipEvent_t before = nullptr;
-        CTO_HIP(hipStreamCreateWithFlags(&own_main, hipStreamNonBlocking));
-        CTO_HIP(hipEventCreateWithFlags(&before, hipEventDisableTiming));
-        CTO_HIP(hipEventRecord(before, nullptr));
-        CTO_HIP(hipStreamWaitEvent(own_main, before, 0));
-        CTO_HIP(hipEventDestroy(before));
-        main = own_main;
-    }
-    hipStream_t copy_back = nullptr;
-    CTO_HIP(hipStreamCreateWithFlags(&copy_back, hipStreamNonBlocking));
-    // a second compute stream for every other chunk, when the caller brought a second pair of handles (cto_run_cfg.aff2)
-    hipStream_t second = nullptr;
-    if (cfg->aff2 && cfg->neg2) {
-        hipEvent_t before = nullptr;
-        CTO_HIP(hipStreamCreateWithFlags(&second, hipStreamNonBlocking));
-        CTO_HIP(hipEventCreateWithFlags(&before, hipEventDisableTiming));
-        CTO_HIP(hipEventRecord(before, main));
-        CTO_HIP(hipStreamWaitEvent(second, before, 0));
-        CTO_HIP(hipEventDestroy(before));
-    }
-    const double t_begin = now_s();
-    std::atomic<int> producers_left{producers};
 
     // The producers share TWO copy streams (CTO_COPY_STREAMS=n; 0: a stream each, as until the end of round 6).  The runtime maps a process's
     // streams onto four hardware queues; with a stream per producer the stream the networks run on shares its queue with one or two copy
@@ -1271,29 +1064,54 @@ static int run_chunks(const cto_run_cfg* cfg, const cto_chunk_job* jobs, int64_t
     // leg: text -> VCF 1.97-1.98 -> 2.04-2.06 M sites/s, with the device tokeniser 1.85 -> 1.93-1.96 M, all-device BAM on two cores 0.56-0.58
     // -> 0.59-0.60 M, BAM -> VCF, REGION jobs and 10 000-site chunks unchanged.  A producer only queues on its stream and waits on its own
     // events, so what another producer queues in between costs it little.
-    static const int shared_n = [] { const char* e = getenv("CTO_COPY_STREAMS"); return e ? atoi(e) : 2; }();
-    struct CopyStreams {                     // (declared before the threads: destroyed after they are joined)
-        std::vector<hipStream_t> v;
-        ~CopyStreams() { for (hipStream_t c : v) { (void)hipStreamSynchronize(c); (void)hipStreamDestroy(c); } }
-    } copy_streams;
-    for (int i = 0; i < shared_n; ++i) {
-        hipStream_t c = nullptr;
-        CTO_HIP(hipStreamCreateWithFlags(&c, hipStreamNonBlocking));
-        copy_streams.v.push_back(c);
+    int open_copy_streams() {
+        static const int shared_n = [] { const char* e = getenv("CTO_COPY_STREAMS"); return e ? atoi(e) : 2; }();
+        std::vector<Stream> v(size_t(std::max(shared_n, 0)));
+        copy.swap(v);
+        for (Stream& c : copy)
+            if (const int rc = c.create()) return rc;
+        return CTO_OK;
     }
-    const std::vector<hipStream_t>& shared_copy = copy_streams.v;
+};
+
+}  // namespace
+
+static int run_chunks(const cto_run_cfg* cfg, const cto_chunk_job* jobs, int64_t n_jobs, void* stream, cto_run_stats* stats) {
+    int rc;
+    if ((rc = check_arguments(cfg, jobs, n_jobs)) != CTO_OK) return rc;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (n_jobs == 0) return CTO_OK;
+    const int producers = std::max(1, cfg->producers), writers = std::max(1, cfg->writers);
+    const int depth = cfg->depth > 0 ? cfg->depth : producers + writers + 2;
+    Run run{cfg, jobs, n_jobs};
+    std::string err;
+    CTO_REQUIRE(run.fasta.open(cfg->ref_fa, &err), CTO_EINVAL, "cto_run_chunks: %s", err.c_str());
+    CTO_REQUIRE(!cfg->indel_regions_bed || !cfg->indel_regions_bed[0] || load_indel_regions(cfg->indel_regions_bed, &run.indel_regions, &err), CTO_EINVAL,
+                "cto_run_chunks: %s", err.c_str());
+    int dev = 0;
+    CTO_HIP(hipGetDevice(&dev));
+    Lease<Slot> slots_back{slot_cache(), &run.slots, [](Slot& s) { s.drop_pack(); }};
+    if ((rc = lease_slots(run, slots_back, dev, depth)) != CTO_OK) return rc;
+    Lease<InflateCtx> ctx_back{inflate_cache(), &run.inflate_ctx, nullptr};
+    lease_inflate_contexts(run, ctx_back, dev);
+    RunStreams streams;                      // (declared before the threads: destroyed after they are joined)
+    if ((rc = streams.open(cfg, static_cast<hipStream_t>(stream))) != CTO_OK) return rc;
+    const hipStream_t main = streams.main, second = streams.second, copy_back = streams.copy_back;
+    const double t_begin = now_s();
+    if ((rc = streams.open_copy_streams()) != CTO_OK) return rc;
+    std::atomic<int> producers_left{producers};
     std::vector<std::thread> threads;
     threads.reserve(size_t(producers + writers));
     struct JoinAll {                         // whatever happens below, a started thread is joined (queues closed first: they all wake up)
         Run& run;
         std::vector<std::thread>& th;
-        ~JoinAll() {
+        void join() {
             run.to_launch.close();
             run.to_write.close();
             run.free_slots.close();
-            for (auto& t : th)
-                if (t.joinable()) t.join();
+            for (auto& t : th) if (t.joinable()) t.join();
         }
+        ~JoinAll() { join(); }
     } join_all{run, threads};
     auto start = [&](auto&& body) -> bool {
         try {
@@ -1305,59 +1123,14 @@ static int run_chunks(const cto_run_cfg* cfg, const cto_chunk_job* jobs, int64_t
         }
     };
     for (int t = 0; t < producers; ++t)
-        if (!start([&run, &producers_left, dev, t, &shared_copy] {
-            hipStream_t copy = nullptr;
-            const bool shared = !shared_copy.empty();
-            tl_pack_threads = run.cfg->pack_threads;                 // the tokeniser's / BAM decoder's own threads per call
-            if (shared) { (void)hipSetDevice(dev); copy = shared_copy[size_t(t) % shared_copy.size()]; }
-            else if (hipSetDevice(dev) != hipSuccess || hipStreamCreateWithFlags(&copy, hipStreamNonBlocking) != hipSuccess) run.fail("producer: no HIP stream");
-            for (;;) {
-                if (run.failed) break;
-                const int64_t j = run.next_job.fetch_add(1);
-                if (j >= run.n_jobs) break;
-                Slot* s = nullptr;
-                if (!run.free_slots.pop(&s)) break;
-                if (run.failed) {                                    // the run failed while this thread waited for a slot: what the slot's
-                    run.free_slots.push(s);                          // last chunk queued on the device may still be running - leave it alone
-                    break;
-                }
-                s->job = j;
-                const double t0 = now_s();
-                bool ok = false;
-                try {
-                    ok = copy && run.produce(s, copy);
-                } catch (const std::exception& e) {                  // bad_alloc on a huge chunk: an error of the run, not of the process
-                    run.fail(std::string("producer: ") + e.what());
-                }
-                { std::lock_guard<std::mutex> g(run.stat_m); run.produce_s += now_s() - t0; }
-                if (ok) run.to_launch.push(s);
-                else run.free_slots.push(s);                         // nothing to call here (or an error: `failed` is set)
-            }
-            if (copy) { (void)hipStreamSynchronize(copy); if (!shared) (void)hipStreamDestroy(copy); }
+        if (!start([&run, &producers_left, dev, copy = streams.copy.empty() ? nullptr : streams.copy[size_t(t) % streams.copy.size()].s] {
+            run.producer(dev, copy);
             if (--producers_left == 0) run.to_launch.close();
         })) {
             if (--producers_left == 0) run.to_launch.close();        // this one never ran
         }
-    for (int t = 0; t < writers; ++t)
-        (void)start([&run, dev] {
-            (void)hipSetDevice(dev);
-            Slot* s = nullptr;
-            while (run.to_write.pop(&s)) {
-                const double t0 = now_s();
-                try {
-                    if (!run.failed) run.finish(s);
-                } catch (const std::exception& e) {
-                    run.fail(std::string("writer: ") + e.what());
-                }
-                { std::lock_guard<std::mutex> g(run.stat_m); run.finish_s += now_s() - t0; }
-                run.free_slots.push(s);
-            }
-        });
+    for (int t = 0; t < writers; ++t) (void)start([&run, dev] { run.writer(dev); });
     if (run.failed) run.free_slots.close();  // a thread did not start: nobody may wait for a slot that no writer will hand back
-    // ---- launcher: this thread ----
-    double launch_s = 0, wait_s = 0;
-    int rc = CTO_OK;
-    int64_t launched = 0;
     // the networks take a stream of sites, not chunks (Run::launch_stream), unless two compute streams take the chunks in turn or the
     // caller turns it off (CTO_TILE_STREAM=0: every chunk is its own launch, as before)
     static const bool stream_off = [] { const char* e = getenv("CTO_TILE_STREAM"); return e && e[0] == '0'; }();
@@ -1372,87 +1145,29 @@ static int run_chunks(const cto_run_cfg* cfg, const cto_chunk_job* jobs, int64_t
         // slot waiting no producer could ever deliver that chunk, so at most depth - 1 wait (the launch that would make it `depth`
         // takes everything that is pending instead)
         run.max_pending = size_t(std::max(0, std::min(4, depth - 1)));
-        (void)hipEventCreate(&run.flush_begin);
-        (void)hipEventCreate(&run.flush_end);
+        (void)run.flush_begin.create();      // without them the flush goes untimed
+        (void)run.flush_end.create();
     }
-    std::vector<Slot*> complete;
-    auto hand_over = [&] {
-        for (Slot* c : complete) {
-            if (run.failed) run.free_slots.push(c); else run.to_write.push(c);
-        }
-        complete.clear();
-    };
-    auto abandon_pending = [&] {             // a failed run: the chunks still waiting for rows give their slots back
-        if (!run.pending.empty()) (void)hipStreamSynchronize(main);
-        for (const Run::Pending& q : run.pending) run.free_slots.push(q.s);
-        run.pending.clear();
-    };
-    for (;;) {
-        Slot* s = nullptr;
-        const double t0 = now_s();
-        if (!run.to_launch.pop(&s)) break;
-        const double t1 = now_s();
-        wait_s += t1 - t0;
-        bool queued = false;
-        if (!run.failed) {
-            int r;
-            if (tile_stream) {
-                r = run.launch_stream(s, main, copy_back, cfg->aff, cfg->neg, &complete);
-                queued = r == CTO_OK || std::any_of(run.pending.begin(), run.pending.end(), [s](const Run::Pending& q) { return q.s == s; });
-            } else {
-                const bool odd = second && (launched++ & 1);
-                r = run.launch(s, odd ? second : main, copy_back, odd ? cfg->aff2 : cfg->aff, odd ? cfg->neg2 : cfg->neg);
-                if (r == CTO_OK) { complete.push_back(s); queued = true; }
-            }
-            if (r != CTO_OK) { run.fail(cto_last_error()); rc = r; }
-        }
-        launch_s += now_s() - t1;
-        if (!queued) {
-            (void)hipStreamSynchronize(main);                         // its buffers may be in use by what was queued before the failure
-            run.free_slots.push(s);
-        }
-        hand_over();
-        if (run.failed) abandon_pending();
-    }
-    if (tile_stream && !run.failed) {
-        const double t1 = now_s();
-        const int r = run.flush_stream(main, copy_back, cfg->aff, cfg->neg, &complete);
-        if (r != CTO_OK) { run.fail(cto_last_error()); rc = r; }
-        launch_s += now_s() - t1;
-        hand_over();
-    }
-    if (run.failed) abandon_pending();
-    run.to_write.close();
-    run.free_slots.close();
-    for (auto& th : threads) th.join();
+    rc = run.launcher(main, second, copy_back, tile_stream);
+    join_all.join();
     (void)hipStreamSynchronize(main);
-    if (second) { (void)hipStreamSynchronize(second); (void)hipStreamDestroy(second); }
+    if (second) (void)hipStreamSynchronize(second);
     (void)hipStreamSynchronize(copy_back);
-    (void)hipStreamDestroy(copy_back);
     if (run.flush_timed) {
         float ms = 0;
-        if (hipEventElapsedTime(&ms, run.flush_begin, run.flush_end) == hipSuccess) run.device_s += ms * 1e-3;
+        if (hipEventElapsedTime(&ms, run.flush_begin, run.flush_end) == hipSuccess) run.st.device_s += ms * 1e-3;
     }
-    if (run.flush_begin) (void)hipEventDestroy(run.flush_begin);
-    if (run.flush_end) (void)hipEventDestroy(run.flush_end);
-    if (own_main) (void)hipStreamDestroy(own_main);
     if (stats) {
+        *stats = run.st;
+        stats->seconds = now_s() - t_begin;
         stats->candidates = run.candidates;
         stats->sites = run.sites;
         stats->rows = run.rows;
         stats->low_coverage = run.low_cov;
         stats->clamped = run.clamped;
-        stats->seconds = now_s() - t_begin;
-        stats->produce_s = run.produce_s;
-        stats->pack_s = run.pack_s;
-        stats->upload_s = run.upload_s;
-        stats->device_s = run.device_s;
         stats->device_inflated = run.device_inflated;
         stats->device_piled = run.device_piled;
         stats->device_tokenised = run.device_tokenised;
-        stats->launch_s = launch_s;
-        stats->launcher_wait_s = wait_s;
-        stats->finish_s = run.finish_s;
     }
     if (run.failed) {
         set_error("cto_run_chunks: %s", run.first_error.c_str());
@@ -1485,14 +1200,8 @@ extern "C" int cto_run_release(void) {
     }
     int cur = 0;
     CTO_HIP(hipGetDevice(&cur));
-    for (auto& sl : drop) {
-        CTO_HIP(hipSetDevice(sl->device));
-        sl.reset();
-    }
-    for (auto& c : drop_ctx) {
-        CTO_HIP(hipSetDevice(c->device));
-        c.reset();
-    }
+    for (auto& sl : drop) { CTO_HIP(hipSetDevice(sl->device)); sl.reset(); }
+    for (auto& c : drop_ctx) { CTO_HIP(hipSetDevice(c->device)); c.reset(); }
     CTO_HIP(hipSetDevice(cur));
     return CTO_OK;
 }

@@ -33,6 +33,7 @@
 #include "realign_internal.h"
 
 using cto_realign::Ends;
+using cto::Event;
 using cto_realign::Window;
 using namespace cto::realign_host;
 

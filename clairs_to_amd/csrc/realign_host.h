@@ -1,5 +1,5 @@
 // Host-side plumbing of the batched realigner's driver (realign_batch.hip), none of it about alignment: the memory of one call (bump
-// arenas on the device and page-locked on the host), objects the library keeps between calls (Kept), an owning event, worker threads
+// arenas on the device and page-locked on the host), objects the library keeps between calls (Kept), worker threads
 // that outlive a call, a thread that frees behind the caller's back, and the stage clock of CTO_REALIGN_TRACE.
 #pragma once
 #include <pthread.h>
@@ -14,6 +14,7 @@
 #include <thread>
 #include <vector>
 #include "common.h"
+#include "hip_buffers.h"
 
 namespace cto {
 namespace realign_host {
@@ -178,17 +179,6 @@ struct ArenaBuf {
 };
 
 // ------------------------------------------------------------------------------------------------------------------------
-// An event that goes with its scope
-struct Event {
-    hipEvent_t e = nullptr;
-    Event() = default;
-    Event(const Event&) = delete;
-    Event& operator=(const Event&) = delete;
-    ~Event() { if (e) (void)hipEventDestroy(e); }
-    int create(unsigned flags = hipEventDefault) { CTO_HIP(hipEventCreateWithFlags(&e, flags)); return CTO_OK; }
-    operator hipEvent_t() const { return e; }
-};
-
 // Side streams kept between calls: creating and destroying four streams and their events cost a call ~1 ms.
 struct StreamSet {
     static constexpr int kMax = 5;
