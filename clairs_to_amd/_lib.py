@@ -85,6 +85,10 @@ class AlleleStats(C.Structure):
                 ("ms_inflate", C.c_double), ("ms_records", C.c_double), ("ms_count", C.c_double)]
 
 
+class GermlineStats(C.Structure):
+    _fields_ = [("n_runs", c_i64), ("n_probes", c_i64), ("host_path", c_i64), ("kernel_ms", C.c_double)]
+
+
 class RunStats(C.Structure):
     _fields_ = [("candidates", c_i64), ("sites", c_i64), ("rows", c_i64), ("low_coverage", c_i64), ("clamped", c_i64), ("seconds", C.c_double),
                 ("produce_s", C.c_double), ("finish_s", C.c_double), ("launch_s", C.c_double), ("launcher_wait_s", C.c_double),
@@ -191,6 +195,7 @@ SYMBOLS = {
     "cto_posterior_from_probs": (C.c_int, [c_vp, C.c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "cto_allele_counts": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, c_vp, c_i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_vp,
                                     c_vp, C.POINTER(AlleleStats)]),
+    "cto_germline_window_dist": (C.c_int, [c_vp, c_vp, c_i64, C.c_int, C.c_int, c_vp, C.POINTER(GermlineStats)]),
 }
 
 for _name, (_res, _args) in SYMBOLS.items():

@@ -772,6 +772,30 @@ int cto_allele_counts(const char* bam_path, const char* bai_path, const char* ct
                       int where /* 0 host, 1 device */, int host_threads, void* stream,
                       int32_t* counts /* n_loci x 4, host */, cto_allele_stats* stats);
 
+/* ----------------------------------------------------------------------------------------------
+ * Germline genotypes (csrc/germline.hip): the window distances of the reference's predictGermlineGenotypes
+ * (src/verdict/predict_germline_genotypes.py:70-154, step 4 of the Verdict chain), over runs of undecided probes.
+ *   c               the mirrored BAFs min(baf, 1 - baf) of the undecided probes, run after run, fp64 on the host; no NaN
+ *   run_off         n_runs + 1 ascending offsets into c, run_off[0] = 0 (a run = the undecided probes of one stretch of equal
+ *                   chromosome names; an empty run is allowed)
+ *   segment_length  --segmentLength, >= 2 (below it the reference raises)
+ *   dist            fp64 on the host, as long as c.  Per run of m values: 1 when m <= 5; otherwise, with L = min(m - 1, segment_length)
+ *                   and H = L / 2, the smallest |median - c[k]| over the medians of c[k-L .. k-1] (when k >= L), c[k+1 .. k+L] (when
+ *                   k < m - L) and c[k-H .. k-1] with c[k+1 .. k+H] (when H <= k < m - H); +inf when none is defined.  A median of an
+ *                   even count is (a + b) / 2: the values are bit for bit numpy's.
+ *   force_host      non-zero: the host code of this call (threads over pieces of runs) instead of the kernel; the same bits
+ *   stats           may be NULL.  host_path = 1 when the host code ran: force_host, or segment_length > CTO_GG_MAX_SEGMENT (what the
+ *                   kernel's LDS tile holds on either side).  kernel_ms: HIP-event time of the kernel.
+ * The kernel: one workgroup per CTO_GG_TILE consecutive probes of one run, the tile and its two flanks in LDS, one wave per probe at a
+ * time, the middle ranks found by counting.  CTO_EINVAL for a NaN, descending offsets or segment_length < 2; CTO_EHIP without a device
+ * unless force_host.  Thread-safe (the device part is serialised).
+ * ---------------------------------------------------------------------------------------------- */
+#define CTO_GG_TILE        64
+#define CTO_GG_MAX_SEGMENT 256
+typedef struct cto_germline_stats { int64_t n_runs, n_probes, host_path; double kernel_ms; } cto_germline_stats;
+int cto_germline_window_dist(const double* c, const int64_t* run_off, int64_t n_runs, int segment_length, int force_host,
+                             double* dist /* host */, cto_germline_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif
