@@ -36,8 +36,8 @@
 // linear record stream are grow-only buffers of 1/4, 1 and 1 budget).  A locus belongs to one chunk and a chunk loads every read
 // that overlaps its span, so nothing crosses chunks and all reads of a name that cover a locus are in its chunk.  Per chunk, on
 // the caller's stream:
-//   cto_bam_chunk_span, cto_bgzf_scan, copy up, cto_bgzf_inflate
-//   k_crc32_blocks, k_linearise, k_chain (bam_records.h: shared with the column pile-up)
+//   cto_bam_chunk_span, cto_bgzf_scan, copy up, cto_bgzf_inflate (inflated_span.h: shared with the chunk pipeline)
+//   k_crc32_blocks, k_linearise, k_chain (bam_records.h's RecordStream: shared with the column pile-up)
 //   k_parse_ac      one lane per record: the filters above, CIGAR lengths (CG:B,I too), the span test
 //   k_entered_*     entered reads in file order (scan.h)
 //   k_name_hash / k_name_insert / k_name_link
@@ -57,19 +57,16 @@
 // Counts come down once per chunk.
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cstdlib>
 #include <cstring>
-#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
-#include <fcntl.h>
-#include <unistd.h>
 #include "bam_records.h"
 #include "common.h"
 #include "hip_buffers.h"
+#include "inflated_span.h"
 #include "pack_internal.h"
 #include "scan.h"
 
@@ -84,56 +81,12 @@ struct AcFlags { int dup, crowded; };
 // (a hash map by name); it is not a damaged chunk.
 constexpr unsigned NAME_PROBE_LIMIT = 1024;
 
-// k_parse of the column pile-up with the allele counter's filters; paired_idx = first entered record with flag bit 1
+// parse_record (bam_records.h) with the allele counter's filters; paired_idx = first entered record with flag bit 1
 __global__ void k_parse_ac(const uint8_t* __restrict__ lin, const uint32_t* __restrict__ rec_off, int n_rec, int tid, int beg0, int end0,
                            AlleleParams pr, DevRead* __restrict__ reads, Flags* fl) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_rec) return;
-    DevRead r{};
-    r.off = rec_off[i];
-    const uint8_t* b = lin + r.off + 4;
-    const int64_t bsz = int64_t(int32_t(ld32(lin + r.off)));
-    const int rtid = int(ld32(b)), pos = int(ld32(b + 4));
-    const int l_name = b[8], mapq = b[9];
-    const int n_cig = int(ld16(b + 12)), flag = int(ld16(b + 14));
-    const int l_seq = int(ld32(b + 16));
-    bool stop = false, ok = false;
-    if (rtid != tid) stop = rtid > tid || rtid < 0;
-    else if (pos >= end0) stop = true;
-    else if (!(mapq < pr.min_mq || (flag & pr.excl_flags) || (flag & pr.req_flags) != pr.req_flags ||
-               ((pr.req_flags & 2) && (((flag & 32) != 0) == ((flag & 16) != 0))) || (flag & 1796) || n_cig == 0 || l_seq <= 0 || pos < 0))
-        ok = true;
-    if (stop) atomicMin(&fl->stop_idx, i);
-    if (ok) {
-        const int64_t need = 32 + int64_t(l_name) + int64_t(n_cig) * 4 + int64_t((l_seq + 1) / 2) + int64_t(l_seq);
-        if (need > bsz) { atomicMin(&fl->err_idx, i); ok = false; }
-    }
-    if (ok) {
-        const uint8_t* cg = b + 32 + l_name;
-        const uint8_t* sq = cg + size_t(n_cig) * 4;
-        const uint8_t* ql = sq + (l_seq + 1) / 2;
-        const DevCigar dc = record_cigar(b, bsz, cg, n_cig, ql, l_seq);
-        const uint8_t* ops = dc.ops;
-        const int n_ops = dc.n_ops;
-        const long long rlen = dc.rlen, qlen = dc.qlen;
-        if (qlen != l_seq || rlen == 0) ok = false;
-        else if (int64_t(pos) + rlen > 0x7fffffffLL) { atomicMin(&fl->err_idx, i); ok = false; }
-        else if (pos + rlen <= beg0) ok = false;
-        if (ok) {
-            r.pos = pos;
-            r.end = int32_t(pos + rlen);
-            r.ops_off = uint32_t(ops - lin);
-            r.n_ops = n_ops;
-            r.seq_off = uint32_t(sq - lin);
-            r.qual_off = uint32_t(ql - lin);
-            r.l_seq = l_seq;
-            r.mapq = uint8_t(mapq);
-            r.rev = (flag & 16) != 0;
-            r.valid = 1;
-            if (flag & 1) atomicMin(&fl->paired_idx, i);
-        }
-    }
-    reads[i] = r;
+    parse_record<false>(lin, rec_off, n_rec, tid, beg0, end0, [=](int flag, int mapq) {
+        return !(mapq < pr.min_mq || (flag & pr.excl_flags) || (flag & pr.req_flags) != pr.req_flags ||
+                 ((pr.req_flags & 2) && (((flag & 32) != 0) == ((flag & 16) != 0))) || (flag & 1796)); }, reads, fl);
 }
 
 // entered = valid and in front of the record that ended the scan; their exclusive scan places them in file order
@@ -277,12 +230,12 @@ __global__ __launch_bounds__(256) void k_count(const uint8_t* __restrict__ lin, 
 
 struct AlleleCtx {
     std::mutex mu;                                                  // one device call at a time: the buffers outlive the calls
-    DevBuf d_in, d_out, lin, up, chain_n, chain_base, rec_off, reads, mark, at, rid, hash, table, prev, counts, z1k, tile_a, tile_tot, aflags;
-    PinBuf h_in, h_status, h_up, h_flags, h_aflags, h_counts;
-    hipEvent_t ev = nullptr, t[4] = {nullptr, nullptr, nullptr, nullptr};
-    bool z1k_ready = false;
+    InflatedSpan span;                                              // the chunk's bytes -> inflated blocks (inflated_span.h)
+    RecordStream rs;                                                // -> record offsets (bam_records.h); the loci ride in its upload block
+    DevBuf reads, mark, at, rid, hash, table, prev, counts, aflags;
+    PinBuf h_aflags, h_counts;
+    Event t[4];
 };
-AlleleCtx g_ac;
 
 enum { CHUNK_DONE = 0, CHUNK_DAMAGED = 1, CHUNK_NOTHING = 2, CHUNK_TOO_LARGE = 3, CHUNK_CROWDED = 4 };
 
@@ -296,138 +249,64 @@ int count_chunk_device(AlleleCtx* cx, const char* bam_path, const char* bai_path
     int64_t fb = 0, fe = 0;
     int rc = cto_bam_chunk_span(bam_path, bai_path, ctg_name, lo, hi, &fb, &fe);
     if (rc != CTO_OK) return rc;
-    const size_t nbytes = fe > fb ? size_t(fe - fb) : 0;
-    if (nbytes == 0) { *outcome = CHUNK_NOTHING; return CTO_OK; }
-    const size_t in_al = (nbytes + CTO_BGZF_PAD + 255) / 256 * 256;
-    size_t cap = nbytes / 2048 + 64;
-    if ((rc = cx->h_in.ensure(in_al + cap * sizeof(cto_bgzf_block)))) return rc;
-    {
-        const int fd = ::open(bam_path, O_RDONLY | O_CLOEXEC);
-        CTO_REQUIRE(fd >= 0, CTO_EINVAL, "cto_allele_counts: cannot open %s", bam_path);
-        size_t got = 0;
-        while (got < nbytes) {
-            const ssize_t r = pread(fd, cx->h_in.as<char>() + got, nbytes - got, off_t(fb) + off_t(got));
-            if (r <= 0) break;
-            got += size_t(r);
-        }
-        ::close(fd);
-        CTO_REQUIRE(got == nbytes, CTO_EINVAL, "cto_allele_counts: short read from %s", bam_path);
-    }
-    int64_t n = 0, out_bytes = 0;
-    for (;;) {
-        memset(cx->h_in.as<char>() + nbytes, 0, in_al - nbytes);
-        n = cto_bgzf_scan(cx->h_in.as<uint8_t>(), nbytes, fb, reinterpret_cast<cto_bgzf_block*>(cx->h_in.as<char>() + in_al), int64_t(cap), &out_bytes);
-        if (n != CTO_ENOMEM || cap > (size_t(1) << 24)) break;
-        cap *= 8;                                              // many tiny blocks
-        if ((rc = cx->h_in.grow_keeping(in_al + cap * sizeof(cto_bgzf_block), nbytes))) return rc;
-    }
+    if (fe <= fb) { *outcome = CHUNK_NOTHING; return CTO_OK; }
+    InflatedSpan& span = cx->span;
+    RecordStream& rs = cx->rs;
+    if ((rc = span.read(bam_path, fb, size_t(fe - fb), "cto_allele_counts: "))) return rc;
+    const int64_t n = span.scan();
     if (n == CTO_EINVAL) { *outcome = CHUNK_DAMAGED; return CTO_OK; }      // a block header that is none
     if (n < 0) return int(n);
     if (n == 0) { *outcome = CHUNK_NOTHING; return CTO_OK; }
-    const auto* blocks = reinterpret_cast<const cto_bgzf_block*>(cx->h_in.as<char>() + in_al);
-    std::vector<int64_t> lin_off(size_t(n) + 1, 0);
-    for (int64_t b = 0; b < n; ++b) lin_off[size_t(b) + 1] = lin_off[size_t(b)] + blocks[b].isize;
-    const int64_t len = lin_off[size_t(n)];
+    SpanTables tables;
+    tables.lay_out(span.blocks(), n);
+    const int64_t len = tables.len;
     if (len >= (int64_t(1) << 32) - 65536 || n >= (int64_t(1) << 30)) { *outcome = CHUNK_TOO_LARGE; return CTO_OK; }
     // record starts the index names inside the span -> offsets into the linear stream
-    std::vector<uint64_t> voffs(size_t(4096 + ((hi - lo) >> 14) + 64));
+    std::vector<uint64_t> voffs;
     int32_t tid = -1;
-    int64_t n_st = CTO_ENOMEM;
-    for (int tries = 0; tries < 4 && n_st == CTO_ENOMEM; ++tries) {
-        if (tries) voffs.resize(voffs.size() * 8);
-        n_st = cto_bam_record_starts(bam_path, bai_path, ctg_name, lo, hi, fb, fe, voffs.data(), int64_t(voffs.size()), &tid);
-    }
+    const int64_t n_st = record_starts(bam_path, bai_path, ctg_name, lo, hi, fb, fe, &voffs, &tid);
     if (n_st < 0) return int(n_st);
-    std::vector<int64_t> starts;
-    for (int64_t i = 0; i < n_st; ++i) {
-        const int64_t coff = int64_t(voffs[size_t(i)] >> 16), uoff = int64_t(voffs[size_t(i)] & 0xffff);
-        int64_t a = 0, b = n;
-        while (a < b) { const int64_t m = (a + b) / 2; if (int64_t(blocks[m].file_off) < coff) a = m + 1; else b = m; }
-        if (a >= n || int64_t(blocks[a].file_off) != coff || uoff > int64_t(blocks[a].isize)) continue;     // outside the span
-        starts.push_back(lin_off[size_t(a)] + uoff);
-    }
-    if (starts.empty()) { *outcome = CHUNK_NOTHING; return CTO_OK; }
-    std::sort(starts.begin(), starts.end());
-    starts.erase(std::unique(starts.begin(), starts.end()), starts.end());
-    const int n_chains = int(starts.size());
-    starts.push_back(len);
+    tables.map_starts(span.blocks(), n, voffs.data(), n_st);
+    if (tables.n_chains == 0) { *outcome = CHUNK_NOTHING; return CTO_OK; }
     std::vector<int32_t> loci0(static_cast<size_t>(n_loci));
     for (int64_t i = 0; i < n_loci; ++i) loci0[size_t(i)] = loci[i] - 1;
 
-    const size_t tbl = size_t(n) * sizeof(cto_bgzf_block), out_al = (size_t(std::max<int64_t>(out_bytes, 256)) + 255) / 256 * 256;
-    if ((rc = cx->d_in.ensure(in_al + tbl)) || (rc = cx->d_out.ensure(out_al + size_t(n) * 4)) || (rc = cx->h_status.ensure(size_t(n) * 4)) ||
-        (rc = cx->lin.ensure(size_t(len) + 64)) || (rc = cx->chain_n.ensure(size_t(n_chains + 1) * 4)) || (rc = cx->chain_base.ensure(size_t(n_chains + 2) * 4)) ||
-        (rc = cx->counts.ensure(size_t(n_loci) * 16)) || (rc = cx->h_counts.ensure(size_t(n_loci) * 16)) || (rc = cx->aflags.ensure(sizeof(AcFlags))) ||
-        (rc = cx->tile_a.ensure(size_t(cdiv(std::max<int64_t>(n_chains, 1), SCAN_TILE) + 1) * 8)) || (rc = cx->tile_tot.ensure(64)) ||
-        (rc = cx->h_flags.ensure(sizeof(Flags))) || (rc = cx->h_aflags.ensure(sizeof(AcFlags))))
+    if ((rc = cx->counts.ensure(size_t(n_loci) * 16)) || (rc = cx->h_counts.ensure(size_t(n_loci) * 16)) || (rc = cx->aflags.ensure(sizeof(AcFlags))) ||
+        (rc = cx->h_aflags.ensure(sizeof(AcFlags))))
         return rc;
-    if (!cx->z1k_ready) {
-        uint32_t z[32];
-        crc32_zero_1k_matrix(z);
-        if ((rc = cx->z1k.ensure(sizeof(z)))) return rc;
-        CTO_HIP(hipMemcpy(cx->z1k.p, z, sizeof(z), hipMemcpyHostToDevice));
-        cx->z1k_ready = true;
-    }
     // ---- copy up + inflate ----
     CTO_HIP(hipEventRecord(cx->t[0], s));
-    CTO_HIP(hipMemcpyAsync(cx->d_in.p, cx->h_in.p, in_al + tbl, hipMemcpyHostToDevice, s));
-    const auto* d_blocks = reinterpret_cast<const cto_bgzf_block*>(cx->d_in.as<char>() + in_al);
-    int* d_status = reinterpret_cast<int*>(cx->d_out.as<char>() + out_al);
-    if ((rc = cto_bgzf_inflate(cx->d_in.p, d_blocks, int(n), cx->d_out.p, d_status, s))) return rc;
-    CTO_HIP(hipMemcpyAsync(cx->h_status.p, d_status, size_t(n) * 4, hipMemcpyDeviceToHost, s));
+    if ((rc = span.inflate(s))) return rc;
     CTO_HIP(hipEventRecord(cx->t[1], s));
-    // ---- one upload of the small tables: flags | linear offsets | record starts | loci ----
-    Flags init{};
-    init.stop_idx = init.err_idx = init.paired_idx = init.skip_idx = 0x7fffffff;
-    const void* up_src[4] = {&init, lin_off.data(), starts.data(), loci0.data()};
-    const size_t up_bytes[4] = {sizeof(Flags), lin_off.size() * 8, starts.size() * 8, loci0.size() * 4};
-    size_t up_off[4], up_total = 0;
-    for (int i = 0; i < 4; ++i) { up_off[i] = up_total; up_total += (up_bytes[i] + 255) / 256 * 256 + 256; }
-    if ((rc = cx->up.ensure(up_total)) || (rc = cx->h_up.ensure(up_total))) return rc;
-    for (int i = 0; i < 4; ++i) memcpy(cx->h_up.as<char>() + up_off[i], up_src[i], up_bytes[i]);
-    CTO_HIP(hipMemcpyAsync(cx->up.p, cx->h_up.p, up_total, hipMemcpyHostToDevice, s));
-    char* const d_up = cx->up.as<char>();
-    Flags* fl = reinterpret_cast<Flags*>(d_up + up_off[0]);
-    const int64_t* d_lin_off = reinterpret_cast<const int64_t*>(d_up + up_off[1]);
-    const int64_t* d_starts = reinterpret_cast<const int64_t*>(d_up + up_off[2]);
-    const int32_t* d_loci = reinterpret_cast<const int32_t*>(d_up + up_off[3]);
-    Flags* hf = cx->h_flags.as<Flags>();
-    const uint8_t* lin = cx->lin.as<uint8_t>();
-    hipLaunchKernelGGL(k_crc32_blocks, dim3(unsigned(std::min<int64_t>(n, 4096))), dim3(64), 0, s, cx->d_out.as<uint8_t>(), d_blocks, int(n),
-                       cx->z1k.as<uint32_t>(), fl);
-    hipLaunchKernelGGL(k_linearise, dim3(unsigned(n)), dim3(256), 0, s, cx->d_out.as<uint8_t>(), d_blocks, d_lin_off, cx->lin.as<uint8_t>());
-    const unsigned cgrid = unsigned(cdiv(n_chains, 64));
-    hipLaunchKernelGGL(k_chain, dim3(cgrid), dim3(64), 0, s, lin, len, d_starts, n_chains, 0, cx->chain_n.as<int>(), nullptr, nullptr, fl);
-    scan_exclusive(s, cx->chain_n.as<int>(), n_chains, cx->chain_base.as<int>(), &fl->n_rec, cx->tile_a.as<long long>(), cx->tile_tot.as<long long>());
-    CTO_HIP(hipGetLastError());
-    CTO_HIP(hipMemcpyAsync(hf, fl, sizeof(Flags), hipMemcpyDeviceToHost, s));
-    CTO_HIP(record_and_wait(cx->ev, s));
+    // ---- the record stream and its boundaries; the loci ride in its upload block ----
+    UploadParts extra;
+    extra.add(loci0.data(), loci0.size() * 4);
+    if ((rc = rs.begin(s, span.d_out.p, span.blocks(), n, tables, extra))) return rc;
+    const Flags* hf = rs.h_flags.as<Flags>();
+    Flags* const fl = rs.fl;
+    const int32_t* d_loci = rs.extra<int32_t>(0);
+    const uint8_t* lin = rs.lin.as<uint8_t>();
     st->n_blocks += n;
     st->inflated_bytes += len;
-    {
-        const int* st0 = cx->h_status.as<int>();
-        for (int64_t b = 0; b < n; ++b)
-            if (st0[b] != 0) { *outcome = CHUNK_DAMAGED; return CTO_OK; }       // the linear stream was built from bytes nobody uses
-    }
+    if (span.first_bad_status() >= 0) { *outcome = CHUNK_DAMAGED; return CTO_OK; }       // the linear stream was built from bytes nobody uses
     if (hf->bad_crc || hf->bad_chain) { *outcome = CHUNK_DAMAGED; return CTO_OK; }
     const int n_rec = hf->n_rec;
     int n_valid = 0;
     CTO_HIP(hipMemsetAsync(cx->counts.p, 0, size_t(n_loci) * 16, s));
     if (n_rec > 0) {
-        if ((rc = cx->rec_off.ensure(size_t(n_rec) * 4)) || (rc = cx->reads.ensure(size_t(n_rec) * sizeof(DevRead))) || (rc = cx->mark.ensure(size_t(n_rec) * 4)) ||
+        if ((rc = cx->reads.ensure(size_t(n_rec) * sizeof(DevRead))) || (rc = cx->mark.ensure(size_t(n_rec) * 4)) ||
             (rc = cx->at.ensure(size_t(n_rec + 1) * 4)) || (rc = cx->rid.ensure(size_t(n_rec) * 4)) || (rc = cx->hash.ensure(size_t(n_rec) * 8)) ||
-            (rc = cx->prev.ensure(size_t(n_rec) * 4)) || (rc = cx->tile_a.ensure(size_t(cdiv(n_rec, SCAN_TILE) + 1) * 8)))
+            (rc = cx->prev.ensure(size_t(n_rec) * 4)))
             return rc;
         unsigned tsize = 64;
         while (tsize < 2u * unsigned(n_rec)) tsize <<= 1;
         if ((rc = cx->table.ensure(size_t(tsize) * 4))) return rc;
         const unsigned rgrid = unsigned(cdiv(n_rec, 128));
-        hipLaunchKernelGGL(k_chain, dim3(cgrid), dim3(64), 0, s, lin, len, d_starts, n_chains, 1, cx->chain_n.as<int>(), cx->chain_base.as<int>(),
-                           cx->rec_off.as<uint32_t>(), fl);
-        hipLaunchKernelGGL(k_parse_ac, dim3(rgrid), dim3(128), 0, s, lin, cx->rec_off.as<uint32_t>(), n_rec, tid, int(lo - 1), int(hi), pr,
+        if ((rc = rs.offsets(s, n_rec))) return rc;
+        hipLaunchKernelGGL(k_parse_ac, dim3(rgrid), dim3(128), 0, s, lin, rs.rec_off.as<uint32_t>(), n_rec, tid, int(lo - 1), int(hi), pr,
                            cx->reads.as<DevRead>(), fl);
         hipLaunchKernelGGL(k_entered_marks, dim3(rgrid), dim3(128), 0, s, cx->reads.as<DevRead>(), n_rec, fl, cx->mark.as<int>());
-        scan_exclusive(s, cx->mark.as<int>(), n_rec, cx->at.as<int>(), &fl->n_valid, cx->tile_a.as<long long>(), cx->tile_tot.as<long long>());
+        if ((rc = rs.scan(s, cx->mark.as<int>(), n_rec, cx->at.as<int>(), &fl->n_valid))) return rc;
         hipLaunchKernelGGL(k_entered_write, dim3(rgrid), dim3(128), 0, s, cx->mark.as<int>(), cx->at.as<int>(), n_rec, cx->rid.as<int>());
         CTO_HIP(hipMemsetAsync(cx->table.p, 0xff, size_t(tsize) * 4, s));
         CTO_HIP(hipMemsetAsync(cx->aflags.p, 0, sizeof(AcFlags), s));
@@ -445,9 +324,9 @@ int count_chunk_device(AlleleCtx* cx, const char* bam_path, const char* bai_path
         CTO_HIP(hipEventRecord(cx->t[2], s));
     }
     CTO_HIP(hipMemcpyAsync(cx->h_counts.p, cx->counts.p, size_t(n_loci) * 16, hipMemcpyDeviceToHost, s));
-    CTO_HIP(hipMemcpyAsync(hf, fl, sizeof(Flags), hipMemcpyDeviceToHost, s));
+    if ((rc = rs.copy_flags(s))) return rc;
     CTO_HIP(hipEventRecord(cx->t[3], s));
-    CTO_HIP(record_and_wait(cx->ev, s));
+    if ((rc = rs.wait(s))) return rc;
     if (n_rec > 0) {
         if (hf->err_idx < hf->stop_idx) { *outcome = CHUNK_DAMAGED; return CTO_OK; }
         if (cx->h_aflags.as<AcFlags>()->crowded) { *outcome = CHUNK_CROWDED; return CTO_OK; }
@@ -524,12 +403,9 @@ extern "C" int cto_allele_counts(const char* bam_path, const char* bai_path, con
             return CTO_OK;
         }
         // ---- device ----
-        std::lock_guard<std::mutex> lock(g_ac.mu);
-        AlleleCtx& cx = g_ac;
-        if (!cx.ev) {
-            for (hipEvent_t& e : cx.t) CTO_HIP(hipEventCreate(&e));
-            CTO_HIP(hipEventCreateWithFlags(&cx.ev, hipEventDisableTiming));
-        }
+        AlleleCtx& cx = process_wide<AlleleCtx>();
+        std::lock_guard<std::mutex> lock(cx.mu);
+        for (Event& e : cx.t) if (!e && (rc = e.create())) return rc;
         hipStream_t s = static_cast<hipStream_t>(stream);
         std::vector<std::pair<int64_t, int64_t>> todo;          // [first, last) loci index, a stack: a chunk found too large is halved
         for (int64_t c = n_chunks; c-- > 0;) todo.push_back({cuts[size_t(c)], cuts[size_t(c) + 1]});

@@ -1,9 +1,12 @@
 // Alignment records on the device, shared by the front ends that read BAM there (pileup.hip: reads -> columns; allelecount.hip:
 // per-locus allele counts): the inflated BGZF blocks of one chunk -> one contiguous record stream, every block checked against the
-// CRC-32 of its gzip trailer, record boundaries from the offsets the .bai names, one DevRead per record.  File-local kernels: each
-// source that includes this header gets its own copies.
+// CRC-32 of its gzip trailer, record boundaries from the offsets the .bai names, one DevRead per record.  RecordStream is the host
+// driver that queues them.  File-local kernels: each source that includes this header gets its own copies.
 #pragma once
+#include "bam_span.h"
 #include "common.h"
+#include "hip_buffers.h"
+#include "scan.h"
 
 namespace {
 
@@ -141,8 +144,11 @@ __device__ __forceinline__ DevCigar record_cigar(const uint8_t* b, int64_t bsz, 
     return DevCigar{ops, n_ops, rlen, qlen, has_skip};
 }
 
-__global__ void k_parse(const uint8_t* __restrict__ lin, const uint32_t* __restrict__ rec_off, int n_rec, int tid, int beg0, int end0,
-                        int excl_flags, int min_mq, DevRead* __restrict__ reads, Flags* fl) {
+// One lane per record: the fixed fields, the consumer's header filter accept(flag, mapq), the CIGAR's lengths, the region test; the
+// first record that ends the region's scan lowers stop_idx.  PILEUP: a missing quality string and the first N operation are noted too.
+template <bool PILEUP, class Accept>
+__device__ __forceinline__ void parse_record(const uint8_t* __restrict__ lin, const uint32_t* __restrict__ rec_off, int n_rec, int tid, int beg0,
+                                             int end0, Accept accept, DevRead* __restrict__ reads, Flags* fl) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_rec) return;
     DevRead r{};
@@ -156,7 +162,7 @@ __global__ void k_parse(const uint8_t* __restrict__ lin, const uint32_t* __restr
     bool stop = false, ok = false;
     if (rtid != tid) stop = rtid > tid || rtid < 0;
     else if (pos >= end0) stop = true;
-    else if (!((flag & excl_flags) || (flag & 4) || mapq < min_mq || n_cig == 0 || l_seq <= 0 || pos < 0 || ((flag & 1) && !(flag & 2)))) ok = true;
+    else ok = accept(flag, mapq) && n_cig != 0 && l_seq > 0 && pos >= 0;
     if (stop) atomicMin(&fl->stop_idx, i);
     if (ok) {
         const int64_t need = 32 + int64_t(l_name) + int64_t(n_cig) * 4 + int64_t((l_seq + 1) / 2) + int64_t(l_seq);
@@ -167,30 +173,35 @@ __global__ void k_parse(const uint8_t* __restrict__ lin, const uint32_t* __restr
         const uint8_t* sq = cg + size_t(n_cig) * 4;
         const uint8_t* ql = sq + (l_seq + 1) / 2;
         const DevCigar dc = record_cigar(b, bsz, cg, n_cig, ql, l_seq);
-        const uint8_t* ops = dc.ops;
-        const int n_ops = dc.n_ops;
-        const long long rlen = dc.rlen, qlen = dc.qlen;
-        const bool has_skip = dc.has_skip;
-        if (qlen != l_seq || rlen == 0) ok = false;
-        else if (int64_t(pos) + rlen > 0x7fffffffLL) { atomicMin(&fl->err_idx, i); ok = false; }
-        else if (pos + rlen <= beg0) ok = false;
+        if (dc.qlen != l_seq || dc.rlen == 0) ok = false;
+        else if (int64_t(pos) + dc.rlen > 0x7fffffffLL) { atomicMin(&fl->err_idx, i); ok = false; }
+        else if (pos + dc.rlen <= beg0) ok = false;
         if (ok) {
             r.pos = pos;
-            r.end = int32_t(pos + rlen);
-            r.ops_off = uint32_t(ops - lin);
-            r.n_ops = n_ops;
+            r.end = int32_t(pos + dc.rlen);
+            r.ops_off = uint32_t(dc.ops - lin);
+            r.n_ops = dc.n_ops;
             r.seq_off = uint32_t(sq - lin);
             r.qual_off = uint32_t(ql - lin);
             r.l_seq = l_seq;
             r.mapq = uint8_t(mapq);
             r.rev = (flag & 16) != 0;
-            r.no_qual = ql[0] == 0xff;
             r.valid = 1;
             if (flag & 1) atomicMin(&fl->paired_idx, i);
-            if (has_skip) atomicMin(&fl->skip_idx, i);
+            if (PILEUP) {
+                r.no_qual = ql[0] == 0xff;
+                if (dc.has_skip) atomicMin(&fl->skip_idx, i);
+            }
         }
     }
     reads[i] = r;
+}
+
+// the column pile-up's filters: unmapped, excluded flags, MAPQ, orphans
+__global__ void k_parse(const uint8_t* __restrict__ lin, const uint32_t* __restrict__ rec_off, int n_rec, int tid, int beg0, int end0,
+                        int excl_flags, int min_mq, DevRead* __restrict__ reads, Flags* fl) {
+    parse_record<true>(lin, rec_off, n_rec, tid, beg0, end0, [=](int flag, int mapq) {
+        return !((flag & excl_flags) || (flag & 4) || mapq < min_mq || ((flag & 1) && !(flag & 2))); }, reads, fl);
 }
 
 // "1024 zero bytes" as a 32 x 32 bit matrix over CRC-32 registers (k_crc32_blocks chains the 64 lanes' partial registers with it)
@@ -199,5 +210,91 @@ inline void crc32_zero_1k_matrix(uint32_t z[32]) {
     for (uint32_t i = 0; i < 256; ++i) { uint32_t c = i; for (int k = 0; k < 8; ++k) c = (c & 1u) ? 0xEDB88320u ^ (c >> 1) : c >> 1; tbl[i] = c; }
     for (int i = 0; i < 32; ++i) { uint32_t c = 1u << i; for (int k = 0; k < 1024; ++k) c = tbl[c & 0xFFu] ^ (c >> 8); z[i] = c; }
 }
+
+// The front half of a chunk on the device, from inflated blocks to record offsets: the buffers, the page-locked mirror of the flags
+// and the event the waits sleep on (record_and_wait: hipStreamSynchronize polls the completion signal from the calling thread, and
+// that thread shares the host's cores with everything else of a run).  One chunk at a time, everything on the caller's stream.
+struct RecordStream {
+    cto::DevBuf lin, counts, base, rec_off, z1k, up;
+    cto::DevBuf tile_a, tile_tot;        // tile sums of the spread-out scans
+    // The chunk's small inputs go up as ONE copy out of page-locked memory: separate hipMemcpyAsync calls from pageable vectors each
+    // pin their source on the fly, under a lock every producer thread of a run shares.
+    cto::PinBuf h_up, h_flags;
+    cto::Event ev;
+    cto::UploadParts parts;              // of the chunk's upload block
+    Flags* fl = nullptr;                 // the chunk's flags on the device (its first part)
+    const int64_t* d_starts = nullptr;
+    int64_t len = 0;
+    int n_chains = 0;
+
+    int init() {                         // before the first wait; begin calls it too
+        if (ev.e) return CTO_OK;
+        uint32_t z[32];                  // "1024 zero bytes" as a bit matrix, once per context
+        crc32_zero_1k_matrix(z);
+        int rc;
+        if ((rc = h_flags.ensure(sizeof(Flags))) || (rc = z1k.ensure(sizeof(z)))) return rc;
+        CTO_HIP(hipMemcpy(z1k.p, z, sizeof(z), hipMemcpyHostToDevice));
+        return ev.create(hipEventDisableTiming);          // last: its handle says that the rest is there
+    }
+    // scan.h's exclusive scan, its tile scratch grown to fit
+    template <class Out> int scan(hipStream_t s, const int* in, int n, Out* out, Out* sum) {
+        int rc;
+        if ((rc = tile_a.ensure(size_t(cto::cdiv(n, SCAN_TILE) + 1) * 8)) || (rc = tile_tot.ensure(64))) return rc;
+        scan_exclusive(s, in, n, out, sum, tile_a.as<long long>(), tile_tot.as<long long>());
+        return CTO_OK;
+    }
+    int copy_flags(hipStream_t s) { CTO_HIP(hipMemcpyAsync(h_flags.p, fl, sizeof(Flags), hipMemcpyDeviceToHost, s)); return CTO_OK; }
+    int wait(hipStream_t s) { CTO_HIP(cto::record_and_wait(ev, s)); return CTO_OK; }
+    int fetch_flags(hipStream_t s) { const int rc = copy_flags(s); return rc != CTO_OK ? rc : wait(s); }
+    void chain(hipStream_t s, int mode) {
+        hipLaunchKernelGGL(k_chain, dim3(unsigned(cto::cdiv(n_chains, 64))), dim3(64), 0, s, lin.as<uint8_t>(), len, d_starts, n_chains, mode,
+                           counts.as<int>(), mode ? base.as<int>() : nullptr, mode ? rec_off.as<uint32_t>() : nullptr, fl);
+    }
+
+    template <class T> T* extra(int i) const { return parts.at<T>(up.p, 4 + i); }       // the caller's i-th part on the device
+
+    // One upload: flags | linear offsets | block table | record starts | the caller's `extra` parts.  Then CRC-32 of every block, the
+    // linear stream, the records of every chain counted and the counts scanned; the flags come back behind one sleeping wait: h_flags
+    // has bad_crc, bad_chain and n_rec for the caller to judge.
+    // `t.n_chains` must be positive and `t.len` below 2^32 - 65536 (record offsets are 32-bit).
+    int begin(hipStream_t s, const void* d_inflated, const cto_bgzf_block* h_blocks, int64_t n_blocks, const cto::SpanTables& t,
+              const cto::UploadParts& extra) {
+        int rc;
+        len = t.len;
+        n_chains = t.n_chains;
+        if ((rc = init()) || (rc = lin.ensure(size_t(len) + 64)) || (rc = counts.ensure(size_t(n_chains + 1) * 4)) ||
+            (rc = base.ensure(size_t(n_chains + 2) * 4)))
+            return rc;
+        Flags clean{};
+        clean.stop_idx = clean.err_idx = clean.paired_idx = clean.skip_idx = 0x7fffffff;
+        *h_flags.as<Flags>() = clean;
+        parts = cto::UploadParts();
+        parts.add(&clean, sizeof(Flags));
+        parts.add(t.lin_off.data(), t.lin_off.size() * 8);
+        parts.add(h_blocks, size_t(n_blocks) * sizeof(cto_bgzf_block));
+        parts.add(t.starts.data(), t.starts.size() * 8);
+        for (int i = 0; i < extra.n; ++i) parts.add(extra.src[i], extra.bytes[i]);
+        if ((rc = up.ensure(parts.total)) || (rc = h_up.ensure(parts.total))) return rc;
+        parts.stage(h_up.as<char>());
+        CTO_HIP(hipMemcpyAsync(up.p, h_up.p, parts.total, hipMemcpyHostToDevice, s));
+        fl = parts.at<Flags>(up.p, 0);
+        const cto_bgzf_block* d_blocks = parts.at<cto_bgzf_block>(up.p, 2);
+        d_starts = parts.at<int64_t>(up.p, 3);
+        const uint8_t* src = static_cast<const uint8_t*>(d_inflated);
+        hipLaunchKernelGGL(k_crc32_blocks, dim3(unsigned(std::min<int64_t>(n_blocks, 4096))), dim3(64), 0, s, src, d_blocks, int(n_blocks),
+                           z1k.as<uint32_t>(), fl);
+        hipLaunchKernelGGL(k_linearise, dim3(unsigned(n_blocks)), dim3(256), 0, s, src, d_blocks, parts.at<int64_t>(up.p, 1), lin.as<uint8_t>());
+        chain(s, 0);
+        if ((rc = scan(s, counts.as<int>(), n_chains, base.as<int>(), &fl->n_rec))) return rc;
+        CTO_HIP(hipGetLastError());
+        return fetch_flags(s);
+    }
+    // the offsets of the chunk's n_rec records, in file order, in rec_off
+    int offsets(hipStream_t s, int n_rec) {
+        const int rc = rec_off.ensure(size_t(n_rec) * 4);
+        if (rc == CTO_OK) chain(s, 1);
+        return rc;
+    }
+};
 
 }  // namespace

@@ -180,16 +180,7 @@ void all_on_host(const double* c, const int64_t* run_off, int64_t n_runs, int se
     for (auto& th : threads) th.join();
 }
 
-struct GgContext {                                             // the device side, one call at a time: the buffers outlive the calls
-    std::mutex mu;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, done = nullptr;
-    PinBuf h_in, h_out;
-    DevBuf d_in, d_out;
-};
-GgContext g_gg;
-
-inline size_t align16(size_t n) { return (n + 15) & ~size_t(15); }
+struct GgContext : BatchCtx {};                                // the device side, one call at a time: the buffers outlive the calls
 
 }  // namespace
 
@@ -223,17 +214,9 @@ extern "C" int cto_germline_window_dist(const double* c, const int64_t* run_off,
 
     // one upload: [tiles | c]
     const size_t off_c = align16(tiles.size() * sizeof(GgTile)), bytes_in = off_c + size_t(n) * 8, bytes_out = size_t(n) * 8;
-    std::lock_guard<std::mutex> lock(g_gg.mu);
-    GgContext& X = g_gg;
-    if (!X.stream) {
-        CTO_HIP(hipStreamCreateWithFlags(&X.stream, hipStreamNonBlocking));
-        CTO_HIP(hipEventCreate(&X.ev0));
-        CTO_HIP(hipEventCreate(&X.ev1));
-        CTO_HIP(hipEventCreate(&X.done));
-    }
-    int rc;
-    if ((rc = X.h_in.ensure(bytes_in)) || (rc = X.d_in.ensure(bytes_in)) || (rc = X.h_out.ensure(bytes_out)) || (rc = X.d_out.ensure(bytes_out)))
-        return rc;
+    GgContext& X = process_wide<GgContext>();
+    std::lock_guard<std::mutex> lock(X.mu);
+    if (const int rc = X.open(bytes_in, bytes_out)) return rc;
     char* h = X.h_in.as<char>();
     memcpy(h, tiles.data(), tiles.size() * sizeof(GgTile));
     memcpy(h + off_c, c, size_t(n) * 8);

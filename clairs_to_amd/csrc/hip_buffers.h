@@ -3,12 +3,14 @@
 #pragma once
 #include <unistd.h>
 #include <cstring>
+#include <mutex>
 #include "common.h"
 
 namespace cto {
 
 // what a buffer grows to when `n` bytes do not fit: room for a quarter more, so that slowly growing chunks reallocate rarely
 inline size_t grown_capacity(size_t n) { return n + n / 4 + 4096; }
+inline size_t align16(size_t n) { return (n + 15) & ~size_t(15); }
 
 struct DevBuf {                          // a device allocation that only grows (its bytes do not survive growth)
     void* p = nullptr;
@@ -74,6 +76,29 @@ struct Event {
     ~Event() { if (e) (void)hipEventDestroy(e); }
     int create(unsigned flags = hipEventDefault) { CTO_HIP(hipEventCreateWithFlags(&e, flags)); return CTO_OK; }
     operator hipEvent_t() const { return e; }
+};
+
+// A context that lives as long as the process (buffers kept from call to call).  Never destroyed: at process exit the HIP runtime
+// may already be gone when static destructors run, and ~DevBuf / ~PinBuf / ~Event would call into it.
+template <class T> T& process_wide() { static T* p = new T(); return *p; }
+
+// The device side of an entry point that runs one batch at a time on a stream of its own and keeps its buffers from call to call
+// (process_wide: the stream stays a raw handle, nothing ever waits for it at exit).  Derive a type per entry point.
+struct BatchCtx {
+    std::mutex mu;
+    hipStream_t stream = nullptr;
+    Event ev0, ev1, done;                // around the kernels; behind the copy back
+    PinBuf h_in, h_out;
+    DevBuf d_in, d_out;
+    int open(size_t bytes_in, size_t bytes_out) {       // under mu: stream and events on first use, room for this batch
+        int rc;
+        if (!stream) {
+            if ((rc = ev0.create()) || (rc = ev1.create()) || (rc = done.create())) return rc;
+            CTO_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        }
+        if ((rc = h_in.ensure(bytes_in)) || (rc = d_in.ensure(bytes_in)) || (rc = h_out.ensure(bytes_out))) return rc;
+        return d_out.ensure(bytes_out);
+    }
 };
 
 // A stream that goes with its scope: what is queued on it is waited for, then it is destroyed.  Whoever queues on it from another

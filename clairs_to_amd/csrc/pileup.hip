@@ -6,7 +6,7 @@
 // listed in its header).  What IS held: every array of the pack equal to cto_pack_from_bam's, bit for bit, on every BAM the test
 // suite writes (tests/test_gpu_pileup.py) - the host reader is the specification of this file.
 //
-// Pipeline (one chunk = one call, all kernels on the caller's stream):
+// Pipeline (one chunk = one call, all kernels on the caller's stream; the first three are bam_records.h's, queued by its RecordStream):
 //   k_linearise     the inflated blocks (256-byte aligned output slots) -> one contiguous record stream
 //   k_chain         record boundaries: every virtual offset the .bai names (chunk starts, the linear index's 16 kb windows) is the
 //                   head of a chain of `block_size` hops walked by one lane; counted, then written in file order
@@ -528,39 +528,25 @@ __global__ void k_keys_str(int n_keys, const KeyRec* __restrict__ key_final, con
 }  // namespace
 
 struct cto_dev_pileup {
-    DevBuf tile_a, tile_b, tile_tot;     // tile sums of the spread-out scans
-    DevBuf lin, counts, base, rec_off, reads, rid, live, diff, slot_col, col_slot, col_off, col_pos, col_ref, cursor, tmp,
-        entries, nkc, keyrec, key_off, key_meta, key_group, key_final, key_col, key_len, str_off, key_str, z1k;
-    bool z1k_ready = false;
-    PinBuf h_flags;                      // page-locked mirror of the flags
+    RecordStream rs;                     // inflated blocks -> record offsets (bam_records.h); its upload block carries the intervals
+                                         // and the reference window too, its event serves every wait of the driver
+    DevBuf tile_b;                       // tile sums of the column scan (next to rs.tile_a, rs.tile_tot)
+    DevBuf reads, rid, live, diff, slot_col, col_slot, col_off, col_pos, col_ref, cursor, tmp,
+        entries, nkc, keyrec, key_off, key_meta, key_group, key_final, key_col, key_len, str_off, key_str;
     PinBuf h_stage;                      // page-locked landing area of the small arrays that go back to the host (a copy to pageable
                                          // memory blocks - and spins - until everything queued in front of it is done)
-    // The chunk's small inputs (flags, block table, linear offsets, record starts, intervals, reference window) go up as ONE copy out
-    // of page-locked memory: six hipMemcpyAsync calls from pageable vectors each pin their source on the fly, under a lock every
-    // producer thread of the run shares.
-    DevBuf up;
-    PinBuf h_up;
-    hipEvent_t ev = nullptr;             // the driver's waits sleep on it (record_and_wait): hipStreamSynchronize polls the completion signal
-                                         // from the calling thread, and that thread shares sixteen host cores with everything else of a run
-    ~cto_dev_pileup() { if (ev) (void)hipEventDestroy(ev); }
 };
 
 extern "C" int cto_dev_pileup_create(cto_dev_pileup** out) try {
     CTO_REQUIRE(out, CTO_EINVAL, "cto_dev_pileup_create: null argument");
     std::unique_ptr<cto_dev_pileup> c(new cto_dev_pileup());
-    int rc;
-    if ((rc = c->h_flags.ensure(sizeof(Flags)))) return rc;
-    CTO_HIP(hipEventCreateWithFlags(&c->ev, hipEventDisableTiming));
+    if (const int rc = c->rs.init()) return rc;
     *out = c.release();
     return CTO_OK;
 }
 CTO_CATCH("cto_dev_pileup_create", int)
 
 extern "C" void cto_dev_pileup_destroy(cto_dev_pileup* c) { delete c; }
-
-// Record starts the index names inside the inflated span: chunk starts of the region's bins and the linear index's windows.
-extern "C" int64_t cto_bam_record_starts(const char* bam_path, const char* bai_path, const char* ctg_name, int64_t start, int64_t end,
-                                         int64_t file_begin, int64_t file_end, uint64_t* voffs, int64_t cap, int32_t* tid_out);
 
 extern "C" int cto_pileup_device(cto_dev_pileup* cx, const void* d_inflated, const cto_bgzf_block* h_blocks, int64_t n_blocks,
                                  const uint64_t* rec_voffs, int64_t n_starts, int32_t tid, int64_t start, int64_t end, const int64_t* bed,
@@ -574,23 +560,11 @@ extern "C" int cto_pileup_device(cto_dev_pileup* cx, const void* d_inflated, con
     *fallback = 0;
     *host_lite = nullptr;
     // ---- host-side tables: block -> linear offset, record starts as linear offsets, requested intervals ----
-    std::vector<int64_t> lin_off(size_t(n_blocks) + 1, 0);
-    for (int64_t b = 0; b < n_blocks; ++b) lin_off[size_t(b) + 1] = lin_off[size_t(b)] + h_blocks[b].isize;
-    const int64_t len = lin_off[size_t(n_blocks)];
-    CTO_REQUIRE(len < (int64_t(1) << 32) - 65536, CTO_EUNSUPPORTED, "cto_pileup_device: more than 4 GiB of alignment records in one chunk");
-    std::vector<int64_t> starts;
-    for (int64_t i = 0; i < n_starts; ++i) {
-        const int64_t coff = int64_t(rec_voffs[i] >> 16), uoff = int64_t(rec_voffs[i] & 0xffff);
-        int64_t lo = 0, hi = n_blocks;
-        while (lo < hi) { const int64_t m = (lo + hi) / 2; if (int64_t(h_blocks[m].file_off) < coff) lo = m + 1; else hi = m; }
-        if (lo >= n_blocks || int64_t(h_blocks[lo].file_off) != coff || uoff > int64_t(h_blocks[lo].isize)) continue;     // outside the span
-        starts.push_back(lin_off[size_t(lo)] + uoff);
-    }
-    CTO_REQUIRE(!starts.empty(), CTO_EINVAL, "cto_pileup_device: no record start inside the inflated span");
-    std::sort(starts.begin(), starts.end());
-    starts.erase(std::unique(starts.begin(), starts.end()), starts.end());
-    const int n_chains = int(starts.size());
-    starts.push_back(len);
+    SpanTables tables;
+    tables.lay_out(h_blocks, n_blocks);
+    tables.map_starts(h_blocks, n_blocks, rec_voffs, n_starts);
+    CTO_REQUIRE(tables.len < (int64_t(1) << 32) - 65536, CTO_EUNSUPPORTED, "cto_pileup_device: more than 4 GiB of alignment records in one chunk");
+    CTO_REQUIRE(tables.n_chains > 0, CTO_EINVAL, "cto_pileup_device: no record start inside the inflated span");
     std::vector<int> ivs;                                        // lo[], hi[], base[] back to back
     {
         std::vector<std::pair<int64_t, int64_t>> v;
@@ -607,18 +581,15 @@ extern "C" int cto_pileup_device(cto_dev_pileup* cx, const void* d_inflated, con
         ivs.push_back(int(total));
     }
     const int n_iv = int((ivs.size() - 1) / 3), total = ivs.back();
-    Flags* hf = cx->h_flags.as<Flags>();
-    Flags* fl = nullptr;                 // the flags on the device (first part of the upload block, set below)
-    auto scan = [&](const int* in, int n, auto* out, auto* sum) -> int {        // scan.h's exclusive scan, its tile scratch grown to fit
-        int rc0;
-        if ((rc0 = cx->tile_a.ensure(size_t(cdiv(n, SCAN_TILE) + 1) * 8)) || (rc0 = cx->tile_tot.ensure(64))) return rc0;
-        scan_exclusive(s, in, n, out, sum, cx->tile_a.as<long long>(), cx->tile_tot.as<long long>());
-        return CTO_OK;
-    };
-    auto fetch_flags = [&]() -> int {
-        CTO_HIP(hipMemcpyAsync(hf, fl, sizeof(Flags), hipMemcpyDeviceToHost, s));
-        CTO_HIP(record_and_wait(cx->ev, s));
-        return CTO_OK;
+    RecordStream& rs = cx->rs;
+    auto point_view = [&] {              // the pack's arrays where the context holds them
+        dev_view->col_pos = cx->col_pos.as<int32_t>();
+        dev_view->col_ref = cx->col_ref.as<uint8_t>();
+        dev_view->col_off = cx->col_off.as<int64_t>();
+        dev_view->key_off = cx->key_off.as<int32_t>();
+        dev_view->entries = cx->entries.as<uint32_t>();
+        dev_view->key_meta = cx->key_meta.as<uint8_t>();
+        dev_view->key_group = cx->key_group.as<int32_t>();
     };
     auto empty_result = [&]() -> int {
         std::unique_ptr<cto_pack> p(new cto_pack());
@@ -633,59 +604,27 @@ extern "C" int cto_pileup_device(cto_dev_pileup* cx, const void* d_inflated, con
             return rc0;
         CTO_HIP(hipMemsetAsync(cx->col_off.p, 0, 64, s));
         CTO_HIP(hipMemsetAsync(cx->key_off.p, 0, 64, s));
-        CTO_HIP(record_and_wait(cx->ev, s));
-        dev_view->col_pos = cx->col_pos.as<int32_t>();
-        dev_view->col_ref = cx->col_ref.as<uint8_t>();
-        dev_view->col_off = cx->col_off.as<int64_t>();
-        dev_view->key_off = cx->key_off.as<int32_t>();
-        dev_view->entries = cx->entries.as<uint32_t>();
-        dev_view->key_meta = cx->key_meta.as<uint8_t>();
-        dev_view->key_group = cx->key_group.as<int32_t>();
+        if ((rc0 = rs.wait(s))) return rc0;
+        point_view();
         *host_lite = p.release();
         return CTO_OK;
     };
     if (total == 0) return empty_result();
     int rc;
-    if ((rc = cx->lin.ensure(size_t(len) + 64)) || (rc = cx->counts.ensure(size_t(n_chains + 1) * 4)) || (rc = cx->base.ensure(size_t(n_chains + 2) * 4)) ||
-        (rc = cx->diff.ensure(size_t(total + 1) * 4)) || (rc = cx->slot_col.ensure(size_t(total) * 4)) ||
+    if ((rc = cx->diff.ensure(size_t(total + 1) * 4)) || (rc = cx->slot_col.ensure(size_t(total) * 4)) ||
         (rc = cx->col_slot.ensure(size_t(total) * 4)) || (rc = cx->col_off.ensure(size_t(total + 1) * 8)))
         return rc;
-    Flags init{};
-    init.stop_idx = init.err_idx = init.paired_idx = init.skip_idx = 0x7fffffff;
-    *hf = init;
-    // ---- one upload: flags | linear offsets | block table | record starts | intervals | reference window (256-byte aligned parts) ----
-    const void* up_src[6] = {&init, lin_off.data(), h_blocks, starts.data(), ivs.data(), ref_seq};
-    const size_t up_bytes[6] = {sizeof(Flags), lin_off.size() * 8, size_t(n_blocks) * sizeof(cto_bgzf_block), starts.size() * 8, ivs.size() * 4, ref_len};
-    size_t up_off[6], up_total = 0;
-    for (int i = 0; i < 6; ++i) { up_off[i] = up_total; up_total += (up_bytes[i] + 255) / 256 * 256 + 256; }
-    if ((rc = cx->up.ensure(up_total)) || (rc = cx->h_up.ensure(up_total))) return rc;
-    for (int i = 0; i < 6; ++i) memcpy(cx->h_up.as<char>() + up_off[i], up_src[i], up_bytes[i]);
-    CTO_HIP(hipMemcpyAsync(cx->up.p, cx->h_up.p, up_total, hipMemcpyHostToDevice, s));
-    char* const d_up = static_cast<char*>(cx->up.p);
-    fl = reinterpret_cast<Flags*>(d_up + up_off[0]);
-    const int64_t* d_lin_off = reinterpret_cast<const int64_t*>(d_up + up_off[1]);
-    const cto_bgzf_block* d_blocks = reinterpret_cast<const cto_bgzf_block*>(d_up + up_off[2]);
-    const int64_t* d_starts = reinterpret_cast<const int64_t*>(d_up + up_off[3]);
-    int* d_ivs = reinterpret_cast<int*>(d_up + up_off[4]);
     CTO_HIP(hipMemsetAsync(cx->diff.p, 0, size_t(total + 1) * 4, s));
-    const uint8_t* lin = cx->lin.as<uint8_t>();
-    if (!cx->z1k_ready) {                                     // "1024 zero bytes" as a bit matrix, once per context
-        uint32_t z[32];
-        crc32_zero_1k_matrix(z);
-        if ((rc = cx->z1k.ensure(sizeof(z)))) return rc;
-        CTO_HIP(hipMemcpy(cx->z1k.p, z, sizeof(z), hipMemcpyHostToDevice));
-        cx->z1k_ready = true;
-    }
-    hipLaunchKernelGGL(k_crc32_blocks, dim3(unsigned(std::min<int64_t>(n_blocks, 4096))), dim3(64), 0, s, static_cast<const uint8_t*>(d_inflated),
-                       d_blocks, int(n_blocks), cx->z1k.as<uint32_t>(), fl);
-    hipLaunchKernelGGL(k_linearise, dim3(unsigned(n_blocks)), dim3(256), 0, s, static_cast<const uint8_t*>(d_inflated), d_blocks,
-                       d_lin_off, cx->lin.as<uint8_t>());
-    // ---- record boundaries ----
-    const unsigned cgrid = unsigned(cdiv(n_chains, 64));
-    hipLaunchKernelGGL(k_chain, dim3(cgrid), dim3(64), 0, s, lin, len, d_starts, n_chains, 0, cx->counts.as<int>(), nullptr, nullptr, fl);
-    if ((rc = scan(cx->counts.as<int>(), n_chains, cx->base.as<int>(), &fl->n_rec))) return rc;
-    CTO_HIP(hipGetLastError());
-    if ((rc = fetch_flags())) return rc;
+    // ---- the record stream and its boundaries; the intervals and the reference window ride in its upload block ----
+    UploadParts extra;
+    extra.add(ivs.data(), ivs.size() * 4);
+    extra.add(ref_seq, ref_len);
+    if ((rc = rs.begin(s, d_inflated, h_blocks, n_blocks, tables, extra))) return rc;
+    const Flags* hf = rs.h_flags.as<Flags>();
+    Flags* const fl = rs.fl;
+    const int* d_ivs = rs.extra<int>(0);
+    const char* d_ref = rs.extra<char>(1);
+    const uint8_t* lin = rs.lin.as<uint8_t>();
     if (hf->bad_crc) {
         set_error("cto_pileup_device: the BGZF block at file offset %llu fails its CRC-32", (unsigned long long)h_blocks[hf->bad_crc - 1].file_off);
         return CTO_EINVAL;
@@ -696,27 +635,24 @@ extern "C" int cto_pileup_device(cto_dev_pileup* cx, const void* d_inflated, con
     }
     const int n_rec = hf->n_rec;
     if (n_rec == 0) return empty_result();
-    if ((rc = cx->rec_off.ensure(size_t(n_rec) * 4)) || (rc = cx->reads.ensure(size_t(n_rec) * sizeof(DevRead))) || (rc = cx->rid.ensure(size_t(n_rec) * 4)) ||
+    if ((rc = cx->reads.ensure(size_t(n_rec) * sizeof(DevRead))) || (rc = cx->rid.ensure(size_t(n_rec) * 4)) ||
         (rc = cx->live.ensure(size_t(n_rec + 1) * 4)))
         return rc;
     CTO_HIP(hipMemsetAsync(cx->live.p, 0, size_t(n_rec + 1) * 4, s));
-    hipLaunchKernelGGL(k_chain, dim3(cgrid), dim3(64), 0, s, lin, len, d_starts, n_chains, 1, cx->counts.as<int>(), cx->base.as<int>(),
-                       cx->rec_off.as<uint32_t>(), fl);
-    hipLaunchKernelGGL(k_parse, dim3(unsigned(cdiv(n_rec, 128))), dim3(128), 0, s, lin, cx->rec_off.as<uint32_t>(), n_rec, tid, int(start - 1), int(end),
+    if ((rc = rs.offsets(s, n_rec))) return rc;
+    hipLaunchKernelGGL(k_parse, dim3(unsigned(cdiv(n_rec, 128))), dim3(128), 0, s, lin, rs.rec_off.as<uint32_t>(), n_rec, tid, int(start - 1), int(end),
                        excl_flags, min_mq, cx->reads.as<DevRead>(), fl);
     hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, s, cx->reads.as<DevRead>(), n_rec, cx->rid.as<int>(), fl);
-    {
-        hipLaunchKernelGGL(k_live_marks, dim3(unsigned(cdiv(n_rec, 128))), dim3(128), 0, s, cx->reads.as<DevRead>(), cx->rid.as<int>(), fl, cx->live.as<int>());
-        hipLaunchKernelGGL(k_live_max, dim3(1), dim3(1024), 0, s, cx->live.as<int>(), fl);
-    }
+    hipLaunchKernelGGL(k_live_marks, dim3(unsigned(cdiv(n_rec, 128))), dim3(128), 0, s, cx->reads.as<DevRead>(), cx->rid.as<int>(), fl, cx->live.as<int>());
+    hipLaunchKernelGGL(k_live_max, dim3(1), dim3(1024), 0, s, cx->live.as<int>(), fl);
     Ivs iv{d_ivs, d_ivs + n_iv, d_ivs + 2 * n_iv, n_iv, total};
     hipLaunchKernelGGL(k_cover, dim3(unsigned(cdiv(n_rec, 128))), dim3(128), 0, s, cx->reads.as<DevRead>(), cx->rid.as<int>(), fl, iv, cx->diff.as<int>());
     {
         const int tiles = int(cdiv(total, SCAN_TILE));
-        if ((rc = cx->tile_a.ensure(size_t(tiles + 1) * 8)) || (rc = cx->tile_b.ensure(size_t(tiles + 1) * 16)) || (rc = cx->tile_tot.ensure(64))) return rc;
-        long long* ta = cx->tile_a.as<long long>();
+        if ((rc = rs.tile_a.ensure(size_t(tiles + 1) * 8)) || (rc = cx->tile_b.ensure(size_t(tiles + 1) * 16)) || (rc = rs.tile_tot.ensure(64))) return rc;
+        long long* ta = rs.tile_a.as<long long>();
         long long* tb = cx->tile_b.as<long long>();
-        long long* tt = cx->tile_tot.as<long long>();
+        long long* tt = rs.tile_tot.as<long long>();
         hipLaunchKernelGGL(k_tile_sums, dim3(unsigned(tiles)), dim3(1024), 0, s, cx->diff.as<int>(), total, ta);
         hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(1024), 0, s, ta, tiles, 1, tt + 2);
         hipLaunchKernelGGL(k_columns_count, dim3(unsigned(tiles)), dim3(1024), 0, s, cx->diff.as<int>(), total, ta, tb);
@@ -725,7 +661,7 @@ extern "C" int cto_pileup_device(cto_dev_pileup* cx, const void* d_inflated, con
                            cx->col_slot.as<int>(), cx->col_off.as<long long>(), fl);
     }
     CTO_HIP(hipGetLastError());
-    if ((rc = fetch_flags())) return rc;
+    if ((rc = rs.fetch_flags(s))) return rc;
     const int lim = hf->stop_idx;
     if (hf->err_idx < lim) { set_error("cto_pileup_device: alignment record shorter than its fields, or running past 2^31 - 1"); return CTO_EINVAL; }
     if (hf->paired_idx < lim || hf->skip_idx < lim || hf->deep_col || (max_depth > 0 && hf->max_live >= max_depth) || hf->max_live >= FILL_LIVE_MAX) {
@@ -740,7 +676,6 @@ extern "C" int cto_pileup_device(cto_dev_pileup* cx, const void* d_inflated, con
         (rc = cx->nkc.ensure(size_t(n_cols + 1) * 4)) || (rc = cx->keyrec.ensure(size_t(n_entries) * sizeof(KeyRec))) || (rc = cx->key_off.ensure(size_t(n_cols + 1) * 4)))
         return rc;
     CTO_HIP(hipMemsetAsync(cx->cursor.p, 0, size_t(n_cols) * 4, s));
-    const char* d_ref = d_up + up_off[5];
     hipLaunchKernelGGL(k_col_meta, dim3(unsigned(cdiv(n_cols, 256))), dim3(256), 0, s, cx->col_slot.as<int>(), n_cols, iv, d_ref, (long long)ref_start,
                        (long long)ref_len, cx->col_pos.as<int32_t>(), cx->col_ref.as<uint8_t>(), fl);
     int live_cap = 64;
@@ -751,9 +686,9 @@ extern "C" int cto_pileup_device(cto_dev_pileup* cx, const void* d_inflated, con
     hipLaunchKernelGGL(k_order, dim3(unsigned(std::min<long long>(cdiv(n_cols, 64), 65536))), dim3(64), 0, s, lin, cx->reads.as<DevRead>(), cx->rid.as<int>(),
                        n_cols, cx->col_off.as<long long>(), cx->cursor.as<int>(), cx->tmp.as<TmpEnt>(), cx->entries.as<uint32_t>(), cx->nkc.as<int>(),
                        cx->keyrec.as<KeyRec>(), max_indel_length, fl);
-    if ((rc = scan(cx->nkc.as<int>(), n_cols, cx->key_off.as<int>(), &fl->n_keys))) return rc;
+    if ((rc = rs.scan(s, cx->nkc.as<int>(), n_cols, cx->key_off.as<int>(), &fl->n_keys))) return rc;
     CTO_HIP(hipGetLastError());
-    if ((rc = fetch_flags())) return rc;
+    if ((rc = rs.fetch_flags(s))) return rc;
     if (hf->ref_oob) { set_error("cto_pileup_device: a covered position lies outside the supplied reference"); return CTO_EINVAL; }
     if (hf->many_keys || hf->deep_col) { *fallback = 1; return CTO_OK; }          // deep_col here: more than FILL_LIVE reads open at a read's start
     const int n_keys = hf->n_keys;
@@ -771,9 +706,9 @@ extern "C" int cto_pileup_device(cto_dev_pileup* cx, const void* d_inflated, con
         hipLaunchKernelGGL(k_keys_meta, dim3(unsigned(cdiv(n_cols, 256))), dim3(256), 0, s, n_cols, cx->col_off.as<long long>(), cx->key_off.as<int>(),
                            cx->keyrec.as<KeyRec>(), cx->col_pos.as<int32_t>(), (long long)ref_start, (long long)ref_len, max_indel_length,
                            cx->key_meta.as<uint8_t>(), cx->key_group.as<int32_t>(), cx->key_final.as<KeyRec>(), cx->key_col.as<int>(), cx->key_len.as<int>());
-        if ((rc = scan(cx->key_len.as<int>(), n_keys, cx->str_off.as<long long>(), &fl->key_str_bytes))) return rc;
+        if ((rc = rs.scan(s, cx->key_len.as<int>(), n_keys, cx->str_off.as<long long>(), &fl->key_str_bytes))) return rc;
         CTO_HIP(hipGetLastError());
-        if ((rc = fetch_flags())) return rc;
+        if ((rc = rs.fetch_flags(s))) return rc;
         const long long sb = hf->key_str_bytes;
         if ((rc = cx->key_str.ensure(size_t(sb) + 16))) return rc;
         hipLaunchKernelGGL(k_keys_str, dim3(unsigned(cdiv(n_keys, 128))), dim3(128), 0, s, n_keys, cx->key_final.as<KeyRec>(), cx->key_col.as<int>(),
@@ -798,20 +733,14 @@ extern "C" int cto_pileup_device(cto_dev_pileup* cx, const void* d_inflated, con
         char* hs = cx->h_stage.as<char>();
         for (int i = 0; i < 7; ++i)
             if (bytes[i]) CTO_HIP(hipMemcpyAsync(hs + off[i], src[i], bytes[i], hipMemcpyDeviceToHost, s));
-        CTO_HIP(record_and_wait(cx->ev, s));
+        if ((rc = rs.wait(s))) return rc;
         for (int i = 0; i < 7; ++i)
             if (bytes[i]) memcpy(dst[i], hs + off[i], bytes[i]);
     }
     dev_view->n_cols = n_cols;
     dev_view->n_entries = n_entries;
     dev_view->n_keys = n_keys;
-    dev_view->col_pos = cx->col_pos.as<int32_t>();
-    dev_view->col_ref = cx->col_ref.as<uint8_t>();
-    dev_view->col_off = cx->col_off.as<int64_t>();
-    dev_view->key_off = cx->key_off.as<int32_t>();
-    dev_view->entries = cx->entries.as<uint32_t>();
-    dev_view->key_meta = cx->key_meta.as<uint8_t>();
-    dev_view->key_group = cx->key_group.as<int32_t>();
+    point_view();
     *host_lite = lite.release();
     return CTO_OK;
 }

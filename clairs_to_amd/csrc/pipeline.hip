@@ -29,8 +29,10 @@
 #include <thread>
 #include <vector>
 
+#include "bam_span.h"
 #include "common.h"
 #include "hip_buffers.h"
+#include "inflated_span.h"
 #include "pack_internal.h"
 #include "run_files.h"
 
@@ -100,16 +102,17 @@ struct Slot {
     ~Slot() { if (tok) cto_dev_tokeniser_destroy(tok); drop_pack(); }
 };
 
-// One chunk's trip through the device inflate (csrc/inflate.hip): the BGZF byte range + block table in page-locked memory, their
-// device copies, the inflated blocks on both sides, and a stream CONFINED to the first `cus` compute units
+// One chunk's trip through the device inflate (csrc/inflate.hip): the BGZF byte range, its block table and the inflated blocks
+// (InflatedSpan), the inflated blocks on the host for the host reader, and a stream CONFINED to the first `cus` compute units
 // (hipExtStreamCreateWithCUMask; tools/cumask_probe.hip: N leading bits = N / 8 CUs of every XCD).  A wave-per-block inflate launch
 // occupies its CUs for tens of milliseconds; unconfined, the networks' block kernels - which need a CU's whole register file -
 // wait for those waves to drain, confined they run on the other CUs.
 struct InflateCtx {
     cto_dev_pileup* pile = nullptr;      // reads -> columns on the device (csrc/pileup.hip), created on first use
     int device = 0, cus = 0;
-    PinBuf h_in, h_out, h_sites;         // h_sites: the chunk's candidate positions on their way up (page-locked like every copy source)
-    DevBuf d_in, d_out;
+    InflatedSpan span;
+    PinBuf h_out, h_sites;               // h_out: the inflated span back on the host (the host reader piles it up); h_sites: the chunk's
+                                         // candidate positions on their way up (page-locked like every copy source)
     Stream stream;                       // (after the buffers: drained before they are freed)
     Event landed;                        // recorded behind the copy back; the producer thread sleeps on it (wait_event)
     int open(int dev, int n_cus) {
@@ -162,27 +165,24 @@ constexpr int REGION_FLANK = 17;                       // flankingBaseNum + 1: t
 
 // A pack in a slot's device buffer: its seven arrays + the chunk's candidate positions in ONE allocation, each part 256-byte aligned
 // with 256 bytes behind it.  The page-locked staging buffer of the upload path has the same layout.
-struct PackLayout {
+struct PackLayout : UploadParts {        // src: the arrays of `v` (host or device) and the site list
     enum { SITES = 7, PARTS = 8 };
-    const void* src[PARTS];              // where the parts come from: the arrays of `v` (host or device) and the site list
-    size_t bytes[PARTS], off[PARTS], total = 0;
-    PackLayout(const cto_pack_view& v, const void* sites, size_t n_sites)
-        : src{v.entries, v.col_pos, v.col_ref, v.col_off, v.key_off, v.key_meta, v.key_group, sites} {
+    PackLayout(const cto_pack_view& v, const void* sites, size_t n_sites) {
         const size_t nc = size_t(v.n_cols), ne = size_t(v.n_entries), nk = size_t(v.n_keys);
+        const void* s[PARTS] = {v.entries, v.col_pos, v.col_ref, v.col_off, v.key_off, v.key_meta, v.key_group, sites};
         const size_t b[PARTS] = {ne * 4, nc * 4, nc, (nc + 1) * 8, (nc + 1) * 4, nk, nk * 4, n_sites * 4};
-        for (int i = 0; i < PARTS; ++i) { bytes[i] = b[i]; off[i] = total; total += (b[i] + 255) / 256 * 256 + 256; }
+        for (int i = 0; i < PARTS; ++i) add(s[i], b[i]);
     }
     // the pointers of `v` (its counts are the caller's) and the site list, in the allocation at `base`
-    void bind(const void* base, cto_pack_view* v, const int32_t** d_site_pos) const {
-        const char* d = static_cast<const char*>(base);
-        v->entries = reinterpret_cast<const uint32_t*>(d + off[0]);
-        v->col_pos = reinterpret_cast<const int32_t*>(d + off[1]);
-        v->col_ref = reinterpret_cast<const uint8_t*>(d + off[2]);
-        v->col_off = reinterpret_cast<const int64_t*>(d + off[3]);
-        v->key_off = reinterpret_cast<const int32_t*>(d + off[4]);
-        v->key_meta = reinterpret_cast<const uint8_t*>(d + off[5]);
-        v->key_group = reinterpret_cast<const int32_t*>(d + off[6]);
-        *d_site_pos = reinterpret_cast<const int32_t*>(d + off[SITES]);
+    void bind(void* base, cto_pack_view* v, const int32_t** d_site_pos) const {
+        v->entries = at<uint32_t>(base, 0);
+        v->col_pos = at<int32_t>(base, 1);
+        v->col_ref = at<uint8_t>(base, 2);
+        v->col_off = at<int64_t>(base, 3);
+        v->key_off = at<int32_t>(base, 4);
+        v->key_meta = at<uint8_t>(base, 5);
+        v->key_group = at<int32_t>(base, 6);
+        *d_site_pos = at<int32_t>(base, SITES);
     }
 };
 
@@ -260,61 +260,36 @@ struct Run {
         const size_t nbytes = fe > fb ? size_t(fe - fb) : 0;
         if (nbytes == 0) return CTO_OK;
         const double Cs = cpu_s();
-        const size_t in_al = (nbytes + CTO_BGZF_PAD + 255) / 256 * 256;
-        size_t cap = nbytes / 2048 + 64;
-        if ((rc = c->h_in.ensure(in_al + cap * sizeof(cto_bgzf_block))) != CTO_OK) return rc;
-        {
-            const File f(j.bam_path);
-            CTO_REQUIRE(f.ok(), CTO_EINVAL, "cannot open %s", j.bam_path);
-            CTO_REQUIRE(read_exact(f.fd, c->h_in.p, nbytes, fb), CTO_EINVAL, "short read from %s", j.bam_path);
-        }
+        InflatedSpan& sp = c->span;
+        if ((rc = sp.read(j.bam_path, fb, nbytes, "")) != CTO_OK) return rc;
         const double T1 = now_s(), C1 = cpu_s();
-        int64_t n = 0, out_bytes = 0;
-        for (;;) {
-            memset(static_cast<char*>(c->h_in.p) + nbytes, 0, in_al - nbytes);
-            n = cto_bgzf_scan(static_cast<const uint8_t*>(c->h_in.p), nbytes, fb, reinterpret_cast<cto_bgzf_block*>(static_cast<char*>(c->h_in.p) + in_al),
-                              int64_t(cap), &out_bytes);
-            if (n != CTO_ENOMEM || cap > (size_t(1) << 24)) break;
-            cap *= 8;                                              // many tiny blocks
-            if ((rc = c->h_in.grow_keeping(in_al + cap * sizeof(cto_bgzf_block), nbytes)) != CTO_OK) return rc;
-        }
+        const int64_t n = sp.scan();
         if (n < 0) return int(n);
         if (n == 0) return CTO_OK;
-        const auto* blocks = reinterpret_cast<const cto_bgzf_block*>(static_cast<char*>(c->h_in.p) + in_al);
-        const size_t tbl = size_t(n) * sizeof(cto_bgzf_block), out_al = (size_t(std::max<int64_t>(out_bytes, 256)) + 255) / 256 * 256;
-        if ((rc = c->d_in.ensure(in_al + tbl)) || (rc = c->d_out.ensure(out_al + size_t(n) * 4)) || (rc = c->h_out.ensure(out_al + size_t(n) * 4))) return rc;
-        const auto all_inflated = [&]() -> int {      // the blocks' status words, once they are back in h_out
-            const int* status = reinterpret_cast<const int*>(static_cast<char*>(c->h_out.p) + out_al);
-            for (int64_t b = 0; b < n; ++b)
-                CTO_REQUIRE(status[b] == 0, CTO_EINVAL, "%s: the BGZF block at file offset %llu does not inflate (status %d)", j.bam_path,
-                            (unsigned long long)blocks[b].file_off, status[b]);
+        const cto_bgzf_block* blocks = sp.blocks();
+        const auto all_inflated = [&]() -> int {      // the blocks' status words, once they are back
+            const int64_t b = sp.first_bad_status();
+            CTO_REQUIRE(b < 0, CTO_EINVAL, "%s: the BGZF block at file offset %llu does not inflate (status %d)", j.bam_path,
+                        (unsigned long long)blocks[b].file_off, sp.h_status.as<int>()[b]);
             return CTO_OK;
         };
         const double T2 = now_s(), C2 = cpu_s();
-        CTO_HIP(hipMemcpyAsync(c->d_in.p, c->h_in.p, in_al + tbl, hipMemcpyHostToDevice, c->stream));
-        if ((rc = cto_bgzf_inflate(c->d_in.p, reinterpret_cast<const cto_bgzf_block*>(static_cast<char*>(c->d_in.p) + in_al), int(n), c->d_out.p,
-                                   reinterpret_cast<int*>(static_cast<char*>(c->d_out.p) + out_al), c->stream)))
-            return rc;
+        if ((rc = sp.inflate(c->stream))) return rc;      // the blocks' status words are on their way back behind it
         if (cfg->device_pileup) {
-            // reads -> columns on the device: only the blocks' status words come back before the pile-up
-            CTO_HIP(hipMemcpyAsync(static_cast<char*>(c->h_out.p) + out_al, static_cast<char*>(c->d_out.p) + out_al, size_t(n) * 4, hipMemcpyDeviceToHost, c->stream));
+            // reads -> columns on the device: only the status words come back before the pile-up
             CTO_HIP(hipEventRecord(c->landed, c->stream));
             CTO_HIP(wait_event(c->landed));
             if ((rc = all_inflated()) != CTO_OK) return rc;
             if (!c->pile && (rc = cto_dev_pileup_create(&c->pile))) return rc;
-            std::vector<uint64_t> voffs(size_t(4096 + ((hi - lo) >> 14) + 64));
+            std::vector<uint64_t> voffs;
             int32_t tid = -1;
-            int64_t n_st = CTO_ENOMEM;
-            for (int tries = 0; tries < 4 && n_st == CTO_ENOMEM; ++tries) {       // an index naming more offsets than expected: a larger table
-                if (tries) voffs.resize(voffs.size() * 8);
-                n_st = cto_bam_record_starts(j.bam_path, nullptr, ctg.c_str(), lo, hi, fb, fe, voffs.data(), int64_t(voffs.size()), &tid);
-            }
+            const int64_t n_st = record_starts(j.bam_path, nullptr, ctg.c_str(), lo, hi, fb, fe, &voffs, &tid);
             if (n_st < 0 && n_st != CTO_ENOMEM) return int(n_st);
             int fallback = n_st <= 0;                                               // still too many: the host reader takes the chunk
             cto_pack_view dvw{};
             cto_pack* lite = nullptr;
             if (!fallback) {
-                rc = cto_pileup_device(c->pile, c->d_out.p, blocks, n, voffs.data(), n_st, tid, lo, hi, iv.empty() ? nullptr : iv.data(), int64_t(iv.size() / 2),
+                rc = cto_pileup_device(c->pile, sp.d_out.p, blocks, n, voffs.data(), n_st, tid, lo, hi, iv.empty() ? nullptr : iv.data(), int64_t(iv.size() / 2),
                                        s->ref.data(), s->ref_start, s->ref.size(), 2316, 0, cfg->max_depth, cfg->max_indel_length, c->stream, &dvw, &lite, &fallback);
                 if (rc != CTO_OK) return rc;
             }
@@ -329,7 +304,8 @@ struct Run {
                 return CTO_OK;
             }
         }
-        CTO_HIP(hipMemcpyAsync(c->h_out.p, c->d_out.p, out_al + size_t(n) * 4, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = c->h_out.ensure(sp.out_al))) return rc;
+        CTO_HIP(hipMemcpyAsync(c->h_out.p, sp.d_out.p, sp.out_al, hipMemcpyDeviceToHost, c->stream));
         CTO_HIP(hipEventRecord(c->landed, c->stream));
         const double T3 = now_s();
         CTO_HIP(wait_event(c->landed));
@@ -337,10 +313,10 @@ struct Run {
         if ((rc = all_inflated()) != CTO_OK) return rc;
         rc = cto_pack_from_bam_inflated(j.bam_path, nullptr, ctg.c_str(), lo, hi, iv.empty() ? nullptr : iv.data(), int64_t(iv.size() / 2), s->ref.data(),
                                         s->ref_start, s->ref.size(), 2316, 0, cfg->max_depth, cfg->max_indel_length,
-                                        static_cast<const uint8_t*>(c->h_out.p), size_t(out_bytes), blocks, n, &s->pack);
+                                        static_cast<const uint8_t*>(c->h_out.p), size_t(sp.out_bytes), blocks, n, &s->pack);
         if (timing)
             fprintf(stderr, "device inflate: %.1f MB in %lld blocks -> %.1f MB: read %.1f ms, scan + alloc %.1f, enqueue %.1f, on the device %.1f, pile-up %.1f\n",
-                    nbytes / 1e6, (long long)n, out_bytes / 1e6, (T1 - T0) * 1e3, (T2 - T1) * 1e3, (T3 - T2) * 1e3, (T4 - T3) * 1e3, (now_s() - T4) * 1e3);
+                    nbytes / 1e6, (long long)n, sp.out_bytes / 1e6, (T1 - T0) * 1e3, (T2 - T1) * 1e3, (T3 - T2) * 1e3, (T4 - T3) * 1e3, (now_s() - T4) * 1e3);
         if (rc == CTO_OK) { *done = 1; ++device_inflated; }
         return rc;
     }
@@ -515,8 +491,7 @@ struct Run {
             s->pack->ext_entries = reinterpret_cast<uint32_t*>(hs);
             s->hv.entries = reinterpret_cast<const uint32_t*>(hs);
         }
-        for (int i = in_place ? 1 : 0; i < PackLayout::PARTS; ++i)
-            if (lay.bytes[i]) memcpy(hs + lay.off[i], lay.src[i], lay.bytes[i]);
+        lay.stage(hs, in_place ? 1 : 0);
         if (hipMemcpyAsync(s->pack_dev.p, hs, lay.total, hipMemcpyHostToDevice, stream) != hipSuccess) { fail("hipMemcpyAsync failed"); return false; }
         s->dv = h;
         lay.bind(s->pack_dev.p, &s->dv, &s->d_site_pos);

@@ -234,12 +234,11 @@ struct cto_pon {
     PinBuf h_in, h_small;
     std::vector<cto_bgzf_block> h_blocks;
     std::vector<int64_t> h_pieces;
-    hipEvent_t ev = nullptr;
+    Event ev;
     size_t slab_in = SLAB_DEFAULT, text_cap = 4 * SLAB_DEFAULT;   // inflated bytes per slab, at most (a BGZF block always fits)
     // lines for the host (cto_pon_host_lines)
     std::string hl_bytes;
     std::vector<int64_t> hl_off{0}, hl_line;
-    ~cto_pon() { if (ev) (void)hipEventDestroy(ev); }
 };
 
 namespace {
@@ -430,7 +429,7 @@ int bgzf_range(Scan& sc, FILE* f, int64_t beg, int64_t end, uint32_t head_skip, 
 extern "C" int cto_pon_create(cto_pon** out) try {
     CTO_REQUIRE(out, CTO_EINVAL, "cto_pon_create: null argument");
     std::unique_ptr<cto_pon> c(new cto_pon());
-    CTO_HIP(hipEventCreateWithFlags(&c->ev, hipEventDisableTiming));
+    if (const int rc = c->ev.create(hipEventDisableTiming)) return rc;
     *out = c.release();
     return CTO_OK;
 }

@@ -310,16 +310,7 @@ bool token_is_alt(const std::string& tok, int kind, size_t ref_len, const char* 
     return false;
 }
 
-struct PfContext {                                             // the device side of cto_postfilter_windows, one batch at a time
-    std::mutex mu;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, done = nullptr;
-    PinBuf h_in, h_out;
-    DevBuf d_in, d_out;
-};
-PfContext g_pf;
-
-inline size_t align16(size_t n) { return (n + 15) & ~size_t(15); }
+struct PfContext : BatchCtx {};                                // the device side of cto_postfilter_windows, one batch at a time
 
 }  // namespace
 
@@ -461,18 +452,9 @@ extern "C" int cto_postfilter_windows(int n_jobs, void* const* jobs, int64_t n_c
     off[6] = off[5] + align16(n_tok * 4);
     off[7] = off[6] + align16(n_tok * 4);
     off[8] = off[7] + align16(n_cols + 1);
-    std::lock_guard<std::mutex> lock(g_pf.mu);
-    PfContext& X = g_pf;
-    if (!X.stream) {
-        CTO_HIP(hipStreamCreateWithFlags(&X.stream, hipStreamNonBlocking));
-        CTO_HIP(hipEventCreate(&X.ev0));
-        CTO_HIP(hipEventCreate(&X.ev1));
-        CTO_HIP(hipEventCreate(&X.done));
-    }
-    int rc;
-    if ((rc = X.h_in.ensure(off[8])) || (rc = X.d_in.ensure(off[8])) || (rc = X.h_out.ensure(n_dev_calls * PF_OUT * 8)) ||
-        (rc = X.d_out.ensure(n_dev_calls * PF_OUT * 8)))
-        return rc;
+    PfContext& X = process_wide<PfContext>();
+    std::lock_guard<std::mutex> lock(X.mu);
+    if (const int rc = X.open(off[8], n_dev_calls * PF_OUT * 8)) return rc;
     char* h = X.h_in.as<char>();
     memcpy(h + off[0], dev_calls.data(), n_dev_calls * sizeof(PfCall));
     uint32_t* h_col_off = reinterpret_cast<uint32_t*>(h + off[1]);

@@ -627,14 +627,13 @@ struct cto_dev_tokeniser {
         col_pos, col_ref, key_meta, key_group, str_off, key_str, row_tiles, codes, tok, flags;
     PinBuf h_text;                       // page-locked: the text on its way up
     PinBuf h_stage;                      // page-locked: everything that comes back
-    hipEvent_t ev = nullptr;             // the waits sleep on it (record_and_wait): hipStreamSynchronize spins, and the producer threads share the cores
-    ~cto_dev_tokeniser() { if (ev) (void)hipEventDestroy(ev); }
+    Event ev;                            // the waits sleep on it (record_and_wait): hipStreamSynchronize spins, and the producer threads share the cores
 };
 
 extern "C" int cto_dev_tokeniser_create(cto_dev_tokeniser** out) try {
     CTO_REQUIRE(out, CTO_EINVAL, "cto_dev_tokeniser_create: null argument");
     std::unique_ptr<cto_dev_tokeniser> c(new cto_dev_tokeniser());
-    CTO_HIP(hipEventCreateWithFlags(&c->ev, hipEventDisableTiming));
+    if (const int rc = c->ev.create(hipEventDisableTiming)) return rc;
     *out = c.release();
     return CTO_OK;
 }

@@ -1,6 +1,7 @@
 """The allele counter's device path (csrc/allelecount.hip) against its host path and the naive rules of tests/allelecountutil.py:
 exactly equal, no chunk declined; a damaged block sends its chunk to the host path."""
 import ctypes as C
+import os
 import shutil
 import struct
 
@@ -96,3 +97,22 @@ def test_many_reads_of_one_name(tmp_path, n_same):
     np.testing.assert_array_equal(got, naive_counts(reads, 0, loci, 20, 20, 0, 2316))
     np.testing.assert_array_equal(got, count_alleles(bam, "c", loci, min_bq=20, min_mq=20, req_flags=0, excl_flags=2316, where="host"))
     assert stats["fallback_chunks"] == 0 and stats["n_chunks"] == 1 and stats["n_reads_entered"] == n_same + 1
+
+
+def test_many_tiny_blocks_grow_the_block_table(tmp_path):
+    """64-byte BGZF payloads: the chunk holds more blocks than the first block table has entries (bytes / 2048 + 64), so the scan has
+    to come back with a table eight times as large - the one loop the pipeline's device path shares"""
+    from clairs_to_amd.allele_counter import count_alleles
+    rng = np.random.default_rng(64)
+    reads = [dict(name="r%03d" % i, flag=0, ref=0, pos=int(p), mapq=60, cigar=[("M", 10), ("I", 2), ("M", 12)],
+                  seq="".join(rng.choice(list("ACGT"), size=24)), qual=[int(q) for q in rng.integers(10, 40, size=24)])
+             for i, p in enumerate(np.sort(rng.integers(0, 370, size=300)))]
+    bam = str(tmp_path / "tiny.bam")
+    write_bam(bam, [("c", 400)], reads, block_payload=64)
+    loci = list(range(3, 400, 8))
+    stats = {}
+    got = count_alleles(bam, "c", loci, min_bq=20, min_mq=20, req_flags=0, excl_flags=2316, where="device", stats=stats)
+    np.testing.assert_array_equal(got, naive_counts(reads, 0, loci, 20, 20, 0, 2316))
+    np.testing.assert_array_equal(got, count_alleles(bam, "c", loci, min_bq=20, min_mq=20, req_flags=0, excl_flags=2316, where="host"))
+    assert stats["fallback_chunks"] == 0 and stats["n_chunks"] == 1
+    assert stats["n_blocks"] > os.path.getsize(bam) // 2048 + 64           # the first table cannot have held them
