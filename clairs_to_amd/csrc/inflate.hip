@@ -7,13 +7,13 @@
 // A DEFLATE stream is decoded serially, symbol by symbol, so the wave works as ONE decoder whose 64 lanes do the wide steps:
 //   * bit reader: the compressed bytes are fetched 256 B at a time (one coalesced dword per lane, the next 256 B already in
 //     flight) and handed to a 64-bit bit buffer dword by dword with v_readlane;
-//   * Huffman decode: codes of up to 10 (literal / length) and 9 (distance) bits - nearly all of them - through a lookup table in
+//   * Huffman decode: codes of up to 9 (literal / length, TBL) and 8 (distance, TBD) bits - nearly all of them - through a lookup table in
 //     LDS indexed by the next bits of the stream, built by all lanes per DEFLATE block; longer codes without a table: the codes
 //     are canonical, so lane L (1..15) holds first_code[L], count[L] and offset[L], bit-reverses the next L bits and tests
 //     first <= code < first + count - exactly one lane hits; a ballot names the length, a readlane fetches offset + code - first,
 //     the symbol comes out of the sorted symbol list held in 5 + 1 registers per lane;
-//   * LZ77 window: the output buffer itself.  Literals are byte stores; matches are queued and resolved 256 at a time, one match
-//     per lane, with loads that bypass the vector L1 (source index (k mod distance) for overlapping copies).
+//   * LZ77 window: the output buffer itself.  Literals are byte stores; matches are queued and resolved 128 at a time (TOK), one match
+//     per lane in rounds of 64, with loads that bypass the vector L1 (source index (k mod distance) for overlapping copies).
 //     A 32 KiB ring in LDS was the first version: 4 wavefronts per CU, and a single decoder wave is a chain of dependent
 //     scalar instructions, branches and one LDS round trip per symbol (500 cycles per symbol measured) - the chip inflated 36
 //     chunks a second.  With 4 KB of LDS per wave, six waves per SIMD take turns on that chain.
@@ -40,7 +40,7 @@
 // window load is a vmcnt(0), stores included.  Matches loaded into LDS slots with global_load_lds_ubyte and stored eight
 // matches later under one wait (the window of 7 000 resident waves does not stay in the L2s; a source byte is a microsecond
 // away and nothing downstream in the stream needs it): 8.7, slower, and not pursued to correctness.  The same idea without the
-// LDS-DMA - matches queued in LDS (destination, source, length) and resolved 256 at a time by all lanes, one match per lane, in
+// LDS-DMA - matches queued in LDS (destination, source, length) and resolved 128 at a time by all lanes, one match per lane, in
 // rounds that respect the dependencies (resolve_matches) - 5.8 (kept).  That it is worth 7 % and not a factor says where the
 // bound is: the decoder is wave-uniform code, ~40 of its ~65 instructions per symbol run on the scalar unit, a CU has ONE scalar
 // unit for its four SIMDs, and 256 CUs x 2.1 GHz / 40 = 13 G symbols/s = 17 GB/s - what is measured.  Waves per SIMD, memory
@@ -454,7 +454,8 @@ extern "C" __global__ __launch_bounds__(64) CTO_INF_ATTR void k_bgzf_inflate(con
             __builtin_amdgcn_wave_barrier();
             if (!huff_build<5>(hl, lens, 288, sorted, lane)) { st = ST_BAD_TABLE; break; }
             huff_table32<TBL, false>(hl, lens, sorted, fo, tab_l, lane);
-            huff_build<1>(hd, lens + 288, 30, sorted, lane);     // an incomplete distance code is legal (one code, or none)
+            // an incomplete distance code is legal (one code, or none); an over-subscribed one is not
+            if (!huff_build<1>(hd, lens + 288, 30, sorted, lane)) { st = ST_BAD_TABLE; break; }
             huff_table32<TBD, true>(hd, lens + 288, sorted, fo, tab_d, lane);
 
             // ---- symbols ----

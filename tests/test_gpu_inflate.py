@@ -1,5 +1,6 @@
 """Device BGZF / DEFLATE decompression (csrc/inflate.hip) against zlib: stored, fixed-code and dynamic-code blocks, literal-heavy and
-match-heavy data, overlapping copies, maximum-size blocks, many blocks per launch, malformed input."""
+match-heavy data, overlapping copies, maximum-size blocks, many blocks per launch, malformed input.
+Streams zlib never writes - hand-assembled ones and libdeflate's - are in test_gpu_inflate_vectors.py (CPU side: test_deflate_vectors.py)."""
 import struct
 import zlib
 
