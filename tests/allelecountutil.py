@@ -7,7 +7,7 @@ import tempfile
 
 import numpy as np
 
-from bamutil import CONSUMES_QUERY, CONSUMES_REF, NT16, ref_len_of, write_bam
+from bamutil import CONSUMES_QUERY, CONSUMES_REF, NT16, effective_cigar, ref_len_of, write_bam
 
 # a numeric chromosome name for the CLI (strcmp puts it in front of chrA); chr1 holds the reads with long CIGARs and is the one
 # contig here that the sub-command's per-contig mode (chr1..22, X) runs
@@ -35,7 +35,9 @@ def _locate(r, p0):
 
 
 def naive_counts(reads, ref_index, positions, min_bq, min_mq, req_flags, excl_flags):
-    """int64 [n, 4]: A, C, G, T at the 1-based positions of reference `ref_index`"""
+    """int64 [n, 4]: A, C, G, T at the 1-based positions of reference `ref_index`; a read counts with its effective CIGAR (the CG tag's
+    operations where the record's field is the long-CIGAR placeholder, bamutil.effective_cigar)"""
+    reads = [dict(r, cigar=effective_cigar(r)) for r in reads]
     entered = []
     for r in reads:
         f = r["flag"]
