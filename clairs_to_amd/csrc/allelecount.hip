@@ -1,7 +1,7 @@
 // Per-locus A / C / G / T counts from a BAM: what
 //   alleleCounter -b BAM -l LOCI -o OUT -m <min_bq> -q <min_mq> -f <req_flags> -F <excl_flags> [--dense-snps]
 // (the first command of the reference's Verdict step, src/cna_germline_tagging.py:56-71; a compiled htslib program) counts for the
-// loci of one contig.  cto_allele_counts is the C entry point; the host path (csrc/bam.cpp, allele_counts_host_range) is the plain
+// loci of one contig.  cto_allele_counts is the C entry point; the host path (csrc/bam.cpp on bam_host.h: allele_counts_host_range) is the plain
 // definition of the rules below and the device path in this file is held equal to it, count for count (tests/test_gpu_allele_counter.py).
 //
 // PARITY UNPINNED against alleleCounter: there is no htslib on the build or GPU machines, so the program cannot be built and run there.

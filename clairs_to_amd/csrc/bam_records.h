@@ -1,7 +1,7 @@
 // Alignment records on the device, shared by the front ends that read BAM there (pileup.hip: reads -> columns; allelecount.hip:
 // per-locus allele counts): the inflated BGZF blocks of one chunk -> one contiguous record stream, every block checked against the
 // CRC-32 of its gzip trailer, record boundaries from the offsets the .bai names, one DevRead per record.  RecordStream is the host
-// driver that queues them.  File-local kernels: each source that includes this header gets its own copies.
+// driver that queues them.  File-local kernels: each source that includes this header gets its own copies.  (Host: bam_host.h.)
 #pragma once
 #include "bam_span.h"
 #include "common.h"

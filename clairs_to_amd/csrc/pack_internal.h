@@ -139,15 +139,11 @@ int pack_from_mpileup_impl(const char* text, size_t len, const char* ref_seq, in
 // streams use (csrc/pipeline.hip: one buffer per chunk slot); csrc/extract.hip
 int extract_candidates_scratch(const cto_pack_view* dp, int min_mq, int min_bq, double snv_min_af, double indel_min_af, double min_coverage,
                                int alt_base_num, int select_indel, uint32_t* scratch, uint8_t* flags, int32_t* depth, void* stream);
-// the chunks of a tabix index (inflated .tbi) that may hold records of contig `ctg` (csrc/bam.cpp, the BAI reader's binning code)
 // Allele counter (the C entry point and the device path: csrc/allelecount.hip; the host rules and the index-based chunk plan sit beside
-// the BAM reader, csrc/bam.cpp).  loci: 1-based, strictly ascending; counts: n_loci x 4 (A C G T), zeroed by the call.
+// the pile-up producer, csrc/bam.cpp).  loci: 1-based, strictly ascending; counts: n_loci x 4 (A C G T), zeroed by the call.
 struct AlleleParams { int min_bq, min_mq, req_flags, excl_flags; };
 int allele_counts_host_range(const char* bam_path, const char* bai_path, const char* ctg_name, const int32_t* loci, int64_t n_loci,
                              const AlleleParams& pr, int32_t* counts, int64_t* n_entered, double* ms_records, double* ms_count);
 int allele_plan_chunks(const char* bam_path, const char* bai_path, const char* ctg_name, const int32_t* loci, int64_t n_loci, int64_t budget,
                        std::vector<int64_t>* cuts);
-
-struct IndexChunk { uint64_t beg, end; };     // virtual offsets: compressed block offset << 16 | offset in the inflated block
-bool tbi_contig_chunks(const uint8_t* tbi, size_t len, const char* ctg, std::vector<IndexChunk>* out, bool* found, std::string* err);
 }  // namespace cto

@@ -17,6 +17,7 @@
 #include "hip_buffers.h"
 #include "scan.h"
 #include "pack_internal.h"
+#include "bam_host.h"
 
 using namespace cto;
 
@@ -185,16 +186,10 @@ __global__ __launch_bounds__(256) void k_pon_parse(const uint8_t* __restrict__ t
 }
 
 bool is_gzip_magic(const uint8_t* p, size_t n) { return n >= 2 && p[0] == 0x1f && p[1] == 0x8b; }
-bool is_bgzf_header(const uint8_t* h, size_t n) {
-    if (n < 18 || h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4)) return false;
-    const size_t xlen = size_t(h[10]) | (size_t(h[11]) << 8);
-    for (size_t i = 0; i + 4 <= xlen && 12 + i + 4 <= n;) {
-        const uint8_t* e = h + 12 + i;
-        const size_t slen = size_t(e[2]) | (size_t(e[3]) << 8);
-        if (e[0] == 'B' && e[1] == 'C' && slen == 2) return true;
-        i += 4 + slen;
-    }
-    return false;
+bool is_bgzf_header(const uint8_t* h, size_t n) {      // of a file's first bytes: the block itself is longer than they are
+    BgzfHeader bh;
+    const BgzfHeader::Status st = bgzf_header(h, n, &bh);
+    return st == BgzfHeader::OK || (st == BgzfHeader::MORE && bh.bsize > 0);
 }
 
 // a whole gzip file in memory (a .tbi): every member inflated; false when zlib rejects it
@@ -532,7 +527,7 @@ int host_gzip(Scan& sc, FILE* f) {
 }
 
 // the inflated .tbi at `path` -> the contig's chunks; false when the index cannot be read or parsed
-bool tbi_chunks(const char* path, size_t size, const char* ctg, std::vector<IndexChunk>* chunks, bool* found) {
+bool tbi_chunks(const char* path, size_t size, const char* ctg, std::vector<Chunk>* chunks, bool* found) {
     std::vector<uint8_t> raw(size), idx;
     FILE* g = fopen(path, "rb");
     if (!g) return false;
@@ -593,7 +588,7 @@ int match_file(cto_pon* c, const char* path, const char* only_contig, int requir
         if (only_contig && c->n_calls > 0 && p.size() >= 3 && p.compare(p.size() - 3, 3, ".gz") == 0 && stat(tbi.c_str(), &tb) == 0) {
             // the contig's chunks only; an index that cannot be read, does not parse or names bytes that are not BGZF is not used: the
             // whole file is scanned instead (the reference falls back the same way when tabix fails, and reads no index without tabix)
-            std::vector<IndexChunk> chunks;
+            std::vector<Chunk> chunks;
             bool found = false;
             if (tbi_chunks(tbi.c_str(), size_t(tb.st_size), only_contig, &chunks, &found)) {
                 st->kind = 1;
@@ -653,7 +648,7 @@ extern "C" int64_t cto_pon_host_lines(cto_pon* c, const char** bytes, const int6
 extern "C" int64_t cto_tbi_contig_chunks(const uint8_t* tbi_file, size_t len, const char* ctg, uint64_t* chunks, int64_t cap) try {
     CTO_REQUIRE(tbi_file && ctg && (chunks || cap == 0), CTO_EINVAL, "cto_tbi_contig_chunks: null argument");
     std::vector<uint8_t> idx;
-    std::vector<IndexChunk> out;
+    std::vector<Chunk> out;
     bool found = false;
     std::string err;
     CTO_REQUIRE(gunzip_mem(tbi_file, len, &idx), CTO_EINVAL, "cto_tbi_contig_chunks: not gzip");

@@ -683,7 +683,7 @@ int  cto_pon_set_calls(cto_pon* ctx, int n_ctg, const char* ctg_bytes, const int
 int  cto_pon_match_file(cto_pon* ctx, const char* path, const char* only_contig, int require_allele, uint8_t* hit, cto_pon_stats* stats,
                         void* stream);
 int64_t cto_pon_host_lines(cto_pon* ctx, const char** bytes, const int64_t** off, const int64_t** line_no);
-/* The chunks of a tabix index that cto_pon_match_file reads for contig `ctg` (the binning index of csrc/bam.cpp's BAI reader, whole contig):
+/* The chunks of a tabix index that cto_pon_match_file reads for contig `ctg` (the binning index of csrc/bam_host.h's BAI reader, whole contig):
  * tbi_file = the .tbi file's bytes (BGZF); chunks[2i], chunks[2i + 1] = begin / end virtual offsets, merged and sorted.  Returns their number
  * (0: the index does not name the contig), CTO_ENOMEM when `cap` pairs do not hold them, CTO_EINVAL when the bytes are not a tabix index. */
 int64_t cto_tbi_contig_chunks(const uint8_t* tbi_file, size_t len, const char* ctg, uint64_t* chunks, int64_t cap);

@@ -1,4 +1,4 @@
-"""Test-only: the BAM files that take the record front end (csrc/bam_records.h on the device, its twins in csrc/bam.cpp on the host)
+"""Test-only: the BAM files that take the record front end (csrc/bam_records.h on the device, BamRegion of csrc/bam_host.h on the host)
 away from the one record shape tests/bamutil.py:write_bam gives by default - auxiliary areas of every layout around CG:B,I, BGZF
 blocks at the seams of the CRC-32 slices, fixed fields at their gates, records whose fields lie - and the naive expectations for them.
 Shared by tests/test_bam_records.py (host) and tests/test_gpu_bam_records.py (device); every file is written once per process.
