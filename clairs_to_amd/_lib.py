@@ -89,6 +89,10 @@ class GermlineStats(C.Structure):
     _fields_ = [("n_runs", c_i64), ("n_probes", c_i64), ("host_path", c_i64), ("kernel_ms", C.c_double)]
 
 
+class AspcfStats(C.Structure):
+    _fields_ = [("n_windows", c_i64), ("n_values", c_i64), ("host_path", c_i64), ("kernel_ms", C.c_double)]
+
+
 class RunStats(C.Structure):
     _fields_ = [("candidates", c_i64), ("sites", c_i64), ("rows", c_i64), ("low_coverage", c_i64), ("clamped", c_i64), ("seconds", C.c_double),
                 ("produce_s", C.c_double), ("finish_s", C.c_double), ("launch_s", C.c_double), ("launcher_wait_s", C.c_double),
@@ -196,6 +200,10 @@ SYMBOLS = {
     "cto_allele_counts": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, c_vp, c_i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_vp,
                                     c_vp, C.POINTER(AlleleStats)]),
     "cto_germline_window_dist": (C.c_int, [c_vp, c_vp, c_i64, C.c_int, C.c_int, c_vp, C.POINTER(GermlineStats)]),
+    "cto_aspcf_windows": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, C.c_int, C.c_double, C.c_int, c_vp, c_vp, C.POINTER(AspcfStats)]),
+    "cto_aspcf_squares": (C.c_int, [c_vp, c_i64, c_vp]),
+    "cto_running_median": (C.c_int, [c_vp, c_i64, C.c_int, c_vp]),
+    "cto_exact_pcf": (C.c_int, [c_vp, c_i64, C.c_int, C.c_double, c_vp]),
 }
 
 for _name, (_res, _args) in SYMBOLS.items():

@@ -796,6 +796,42 @@ typedef struct cto_germline_stats { int64_t n_runs, n_probes, host_path; double 
 int cto_germline_window_dist(const double* c, const int64_t* run_off, int64_t n_runs, int segment_length, int force_host,
                              double* dist /* host */, cto_germline_stats* stats);
 
+/* ----------------------------------------------------------------------------------------------
+ * ASPCF (csrc/aspcf.hip): the segmentation step of the Verdict chain (src/verdict/aspcf.py of the reference).  The rules of the
+ * recurrence are listed at the top of csrc/aspcf.hip and derived in DESIGN.md "ASPCF".
+ *
+ * cto_aspcf_windows: the recurrence of aspcfpart over independent windows of one chromosome's heterozygous probes.
+ *   y1, y2          the averaged winsorised logR and the flipped BAF of the chromosome, n values each, fp64 on the host; finite
+ *   win_lo, win_hi  n_win windows [lo, hi) into them, in any order, overlapping or not; hi - lo <= CTO_ASPCF_MAX_WINDOW.  A window
+ *                   shorter than 2 * kmin has no fit: its outputs are zeros.
+ *   v1, v2          per window the divisors sd1 ** 2 and sd2 ** 2, computed by the caller as the reference computes them; positive
+ *   kmin, gamma     the shortest segment (>= 1; the sums of the first kmin values are taken in order, which is numpy's order below 8:
+ *                   the reference uses 6) and the penalty
+ *   best_split      int32, best_cost fp64 (may be NULL): per window hi - lo values, window after window.  The traceback
+ *                   (n = hi - lo; while n > 0: n = best_split[n - 1]) is the caller's.
+ *   force_host      non-zero: the host code of this call (threads over windows) instead of the kernel; the same bits
+ *   stats           may be NULL.  kernel_ms: HIP-event time of the kernel.
+ * Both paths read the same prepared numbers (the squares as libm's pow(x, 2.0), the whole-prefix costs): the kernel squares nothing.
+ * The kernel: one workgroup per window, the slots dealt round-robin over 256 threads and kept in registers, a workgroup arg-min per
+ * step.  CTO_EINVAL for a value that is NaN or infinite, a divisor that is not positive, a window longer than the cap or outside
+ * the arrays, kmin < 1; CTO_EHIP without a device unless force_host.  Thread-safe (the device part is serialised).
+ *
+ * cto_running_median: medianFilter of the reference, scipy.ndimage.median_filter(x, size, mode = 'reflect') with size = 2 k + 1, cut
+ * to n (n odd) or n - 1 (n even) when that exceeds n.  The size is odd: every output is one of the inputs.  Host only.  CTO_EINVAL
+ * for a NaN (scipy orders it by no stated rule).
+ *
+ * cto_exact_pcf: exactPcf of the reference for n >= 2 * kmin values (below that the caller takes np.mean; CTO_EINVAL here), the
+ * single-track form of the recurrence, with its traceback: yhat holds every value's segment average.  Host only.
+ * ---------------------------------------------------------------------------------------------- */
+#define CTO_ASPCF_MAX_WINDOW 1000
+typedef struct cto_aspcf_stats { int64_t n_windows, n_values, host_path; double kernel_ms; } cto_aspcf_stats;
+int cto_aspcf_windows(const double* y1, const double* y2, int64_t n, const int64_t* win_lo, const int64_t* win_hi, int64_t n_win,
+                      const double* v1, const double* v2, int kmin, double gamma, int force_host,
+                      int32_t* best_split /* host */, double* best_cost /* host, may be NULL */, cto_aspcf_stats* stats);
+int cto_aspcf_squares(const double* x, int64_t n, double* out);       /* pow(x, 2.0) as cto_aspcf_windows prepares it; for tests */
+int cto_running_median(const double* x, int64_t n, int k, double* out);
+int cto_exact_pcf(const double* y, int64_t n, int kmin, double gamma, double* yhat);
+
 #ifdef __cplusplus
 }
 #endif
