@@ -15,12 +15,6 @@ namespace cto {
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
-// Row padding (floats) of the packed GRU weight matrices [3H][KP + H + pad]: see gru_kernel.h
-#ifndef CTO_GRU_WPAD
-#define CTO_GRU_WPAD 32
-#endif
-constexpr int GRU_WPAD = CTO_GRU_WPAD;
-
 // Workgroup barrier for LDS-only hand-offs.  `__syncthreads()` is a workgroup-scope release/acquire fence: it drains EVERY
 // outstanding memory operation (s_waitcnt vmcnt(0) lgkmcnt(0)) before s_barrier, so weight fragments that were requested to
 // "fly under the barrier" are waited for right there - one exposed L2 round trip per barrier.  Waves of these kernels only talk

@@ -17,16 +17,14 @@ using namespace cto;
 
 // The recurrent kernels live in their own translation unit (gru.hip): co-compiling them with the CvT kernels changed
 // their register allocation and cost up to 4 % from one unrelated edit to the next.
-int launch_gru_layer1(hipStream_t s, const float* x, const float* W, const float* Wf, const float* bias, float* out, int64_t B);
-bool gru_layer1_takes_raw();
+int launch_gru_layer1(hipStream_t s, const float* x, const float* Wf, const float* bias, float* out, int64_t B);
 int launch_gru_layer1_raw(hipStream_t s, const int16_t* x_raw, const int32_t* site_info, int which, int min_rescale_cov, const float* Wf,
                           const float* bias, float* out, int64_t B);
 int launch_gru_layer2_fc1_split(hipStream_t s, const float* x, const void* Wp, const float* bias, const void* Fp, float* fc1_part,
                                 int64_t B, bool f16, const float* scale5);
 int launch_gru_layer1_split(hipStream_t s, const float* x, const void* Wp, const float* bias, float* out, int64_t B, bool f16,
                             const float* scale5);
-int launch_gru_layer2_fc1(hipStream_t s, const float* x, const float* W, const float* Wf, const float* bias, const float* fc1w,
-                          const float* fc1f, float* fc1_part, int64_t B);
+int launch_gru_layer2_fc1(hipStream_t s, const float* x, const float* Wf, const float* bias, const float* fc1f, float* fc1_part, int64_t B);
 
 
 struct cto_weights {
@@ -62,7 +60,7 @@ struct Arena {
 };
 
 struct HeadDev {          // fc1 -> SELU -> K x (fc2 -> SELU -> fc3 -> SELU)
-    float *w1 = nullptr, *b1 = nullptr;   // [128][K1]
+    float *w1 = nullptr, *b1 = nullptr;   // [128][K1]; w1 is null in a BiGRU handle, whose fc1 runs inside layer 2 out of f1f
     float* w1p = nullptr;                 // CvT: fc1 over the LDS image of the last block's tile ([128][KCH1*16]), or null
     float *w2 = nullptr, *b2 = nullptr;   // [K*128][128]
     float *w3 = nullptr, *b3 = nullptr;   // [K][2][128]
@@ -94,8 +92,8 @@ struct cto_model {
     // CvT
     StageDev st[3];
     // BiGRU
-    float *gw1 = nullptr, *gb1 = nullptr, *gw2 = nullptr, *gb2 = nullptr;
-    float *gw1f = nullptr, *gw2f = nullptr, *f1f = nullptr;     // the recurrent weights and the fused fc1 in fragment order (rotated kernels)
+    float *gb1 = nullptr, *gb2 = nullptr;
+    float *gw1f = nullptr, *gw2f = nullptr, *f1f = nullptr;     // the recurrent weights and the fused fc1 in fragment order (gru_kernel.h)
     float *gw1_split = nullptr, *gw2_split = nullptr, *f1_split = nullptr;     // layer 2 / fc1 as (hi, lo) 16-bit fragments: CTO_GRU_SPLIT=f16|bf16 (experiment)
     bool split_f16 = false;
     float split_sc1[5] = {1.f, 1.f, 1.f, 1.f, 1.f}, split_sc2[5] = {1.f, 1.f, 1.f, 1.f, 1.f};   // GruSplitScale of layer 1 / layer 2 (gru_split_kernel.h)
@@ -158,12 +156,13 @@ std::vector<float> pack_fragments(const float* W, int ntiles, int kch) {
     return f;
 }
 
-int build_head(const cto_weights* w, const char* const* names, int K, int k1, const std::vector<float>& w1perm,
+// w1perm: row-major fc1 for the unfused CvT tail, or null where fc1 runs elsewhere (BiGRU)
+int build_head(const cto_weights* w, const char* const* names, int K, int k1, const std::vector<float>* w1perm,
                Arena& a, HeadDev& h) {
     int rc = CTO_OK;
     h.k1 = k1;
     GETW(b1, "fc1.bias", 128);
-    if ((rc = a.upload(w1perm, &h.w1)) != CTO_OK) return rc;
+    if (w1perm && (rc = a.upload(*w1perm, &h.w1)) != CTO_OK) return rc;
     if ((rc = a.upload(*b1, &h.b1)) != CTO_OK) return rc;
     std::vector<float> w2(size_t(K) * 128 * 128), b2(size_t(K) * 128), w3(size_t(K) * 2 * 128), b3(size_t(K) * 2);
     for (int k = 0; k < K; ++k) {
@@ -494,7 +493,7 @@ int cvt_forward(cto_model* m, const float* x, int64_t B, float* logits, hipStrea
     return run_head(m, s, in, B, logits);
 }
 
-int prof_begin(cto_model* m, hipStream_t s, hipEvent_t* e0, hipEvent_t* e1) {
+int prof_begin(hipStream_t s, hipEvent_t* e0, hipEvent_t* e1) {
     CTO_HIP(hipEventCreate(e0));
     CTO_HIP(hipEventCreate(e1));
     CTO_HIP(hipEventRecord(*e0, s));
@@ -504,19 +503,19 @@ int prof_begin(cto_model* m, hipStream_t s, hipEvent_t* e0, hipEvent_t* e1) {
 int bigru_forward(cto_model* m, const float* x, int64_t B, float* logits, hipStream_t s, const RawIn* raw = nullptr) {
     int rc;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (m->prof_all && (rc = prof_begin(m, s, &e0, &e1))) return rc;
+    if (m->prof_all && (rc = prof_begin(s, &e0, &e1))) return rc;
     if (raw) rc = launch_gru_layer1_raw(s, raw->x, raw->site_info, raw->which, raw->min_rescale_cov, m->gw1f, m->gb1, m->b_h, B);
     else if (m->gw1_split) rc = launch_gru_layer1_split(s, x, m->gw1_split, m->gb1, m->b_h, B, m->split_f16, m->split_sc1);
-    else rc = launch_gru_layer1(s, x, m->gw1, m->gw1f, m->gb1, m->b_h, B);
+    else rc = launch_gru_layer1(s, x, m->gw1f, m->gb1, m->b_h, B);
     if (rc) return rc;
     if (m->prof_all) {
         CTO_HIP(hipEventRecord(e1, s));
         m->prof_ev1.emplace_back(e0, e1);
     }
-    if (m->prof && (rc = prof_begin(m, s, &e0, &e1))) return rc;
+    if (m->prof && (rc = prof_begin(s, &e0, &e1))) return rc;
     // layer 2 with the head's fc1 folded in: writes one partial [B][128] slab per direction into b_slab
     if (m->gw2_split) rc = launch_gru_layer2_fc1_split(s, m->b_h, m->gw2_split, m->gb2, m->f1_split, m->b_slab, B, m->split_f16, m->split_sc2);
-    else rc = launch_gru_layer2_fc1(s, m->b_h, m->gw2, m->gw2f, m->gb2, m->head.w1, m->f1f, m->b_slab, B);
+    else rc = launch_gru_layer2_fc1(s, m->b_h, m->gw2f, m->gb2, m->f1f, m->b_slab, B);
     if (rc) return rc;
     if (m->prof) {
         CTO_HIP(hipEventRecord(e1, s));
@@ -525,14 +524,15 @@ int bigru_forward(cto_model* m, const float* x, int64_t B, float* logits, hipStr
     return run_head(m, s, nullptr, B, logits);
 }
 
-// [W_ih | W_hh] per gate row, W_ih zero-padded to KP; bias rows: r (b_ir + b_hr), z (b_iz + b_hz), b_in, b_hn
-// Wfout: the same weights in the order the rotated kernel's lanes read them, [dir][wave][16-wide chunk][nb][gate][lane][4] with lane
+// bias rows: r (b_ir + b_hr), z (b_iz + b_hz), b_in, b_hn
+// Wfout: [W_ih | W_hh] per gate row, W_ih zero-padded to kp (built row-major here on the host only, as the source of this order), in
+// the order the recurrent kernel's lanes read them, [dir][wave][16-wide chunk][nb][gate][lane][4] with lane
 // (j, kg) holding row  gate * H + (wave * NB + nb) * 16 + j,  k = 16 c + 4 kg .. + 3  of [W_ih (zero-padded to kp) | W_hh]; when the
 // last x chunk holds at most four real channels (layer 1: 34 -> channels 32, 33) it is ONE k-step whose lane group kg holds
 // k = 16 c + kg in element 0 (gru_kernel.h: TAIL1)
-int pack_gru(const cto_weights* w, const std::string& base, int kin, int kp, int H, Arena& a, float** Wout, float** bout, float** Wfout) {
+int pack_gru(const cto_weights* w, const std::string& base, int kin, int kp, int H, Arena& a, float** bout, float** Wfout) {
     int rc = CTO_OK;
-    const int KT = kp + H + GRU_WPAD;
+    const int KT = kp + H;
     const int NB = H / 64, NX = kp / 16, NC = NX + H / 16;
     const bool tail1 = (kin % 16 != 0) && (kin - 16 * (NX - 1) <= 4);
     std::vector<float> W(size_t(2) * 3 * H * KT, 0.f), bv(size_t(2) * 4 * H), Wf(size_t(2) * 4 * NC * NB * 3 * 256, 0.f);
@@ -566,7 +566,6 @@ int pack_gru(const cto_weights* w, const std::string& base, int kin, int kp, int
             b[3 * H + j] = (*bhh)[size_t(2 * H + j)];
         }
     }
-    if ((rc = a.upload(W, Wout)) != CTO_OK) return rc;
     if ((rc = a.upload(Wf, Wfout)) != CTO_OK) return rc;
     return a.upload(bv, bout);
 }
@@ -832,7 +831,7 @@ extern "C" int cto_cvt_create_ex(const cto_weights* w, const cto_cvt_cfg* cfg, i
             for (int c = 0; c < C3; ++c)
                 for (int ww = 0; ww < W3; ++ww) v[size_t(n) * k1 + ww * C3 + c] = (*f1)[size_t(n) * k1 + c * W3 + ww];
         static const char* const names[6] = {"a", "c", "g", "t", "i", "d"};
-        if ((rc = build_head(w, names, m->n_out, k1, v, a, m->head))) return fail(rc);
+        if ((rc = build_head(w, names, m->n_out, k1, &v, a, m->head))) return fail(rc);
         if (C3 == 128 && W3 == 5) {      // fc1 over the LDS image of the last block's tile: k = w * RS + c
             using G = CvtBlockGeom<128, 5, 3, 16>;
             const int KP = G::KCH1 * 16;
@@ -866,13 +865,13 @@ extern "C" int cto_bigru_create_ex(const cto_weights* w, int n_out, int split_mo
     m->n_out = n_out;
     int rc = CTO_OK;
     auto fail = [&](int code) { return code; };
-    if ((rc = pack_gru(w, "lstm", 34, 48, 128, m->arena, &m->gw1, &m->gb1, &m->gw1f))) return fail(rc);
-    if ((rc = pack_gru(w, "lstm_2", 256, 256, 192, m->arena, &m->gw2, &m->gb2, &m->gw2f))) return fail(rc);
+    if ((rc = pack_gru(w, "lstm", 34, 48, 128, m->arena, &m->gb1, &m->gw1f))) return fail(rc);
+    if ((rc = pack_gru(w, "lstm_2", 256, 256, 192, m->arena, &m->gb2, &m->gw2f))) return fail(rc);
     const int k1 = 33 * 384;
     {
         GETW(f1, "fc1.weight", int64_t(128) * k1);
         static const char* const names[6] = {"na", "nc", "ng", "nt", "ni", "nd"};
-        if ((rc = build_head(w, names, n_out, k1, *f1, m->arena, m->head))) return fail(rc);
+        if ((rc = build_head(w, names, n_out, k1, nullptr, m->arena, m->head))) return fail(rc);
         if ((rc = m->arena.upload(pack_fc1_fragments(*f1, 192), &m->f1f))) return fail(rc);
         // experiment (side channel, never the default): layer 2 + fc1 on split 16-bit operands, three f16 / bf16 MFMA passes per product
         const char* e = split_mode == CTO_SPLIT_ENV ? getenv("CTO_GRU_SPLIT") : split_mode == CTO_SPLIT_F16 ? "f16" : split_mode == CTO_SPLIT_BF16 ? "bf16" : nullptr;
@@ -893,23 +892,24 @@ extern "C" int cto_bigru_create_ex(const cto_weights* w, int n_out, int split_mo
     return CTO_OK;
 }
 
-extern "C" int cto_model_forward(cto_model* m, const float* x, int64_t B, float* logits, void* stream) {
-    CTO_REQUIRE(m && x && logits && B >= 0, CTO_EINVAL, "cto_model_forward: bad argument");
+namespace {
+// what both forward entry points check and prepare; `fn` is the entry point's name for the error texts
+int forward_preamble(const char* fn, cto_model* m, bool args_ok, int64_t B) {
+    CTO_REQUIRE(args_ok, CTO_EINVAL, "%s: bad argument", fn);
     CTO_REQUIRE(B * 33 < (int64_t(1) << 31) / 640, CTO_EUNSUPPORTED, "batch too large for 32-bit row indices; split it");
     if (B == 0) return CTO_OK;
-    {
-        int dev = -1;
-        CTO_HIP(hipGetDevice(&dev));
-        CTO_REQUIRE(dev == m->device, CTO_EINVAL, "cto_model_forward: model lives on device %d but device %d is current (one process per GPU)",
-                    m->device, dev);
-    }
-    int rc = ensure_ws(m, B);
-    if (rc != CTO_OK) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (m->kind == 1) return bigru_forward(m, x, B, logits, s);
+    int dev = -1;
+    CTO_HIP(hipGetDevice(&dev));
+    CTO_REQUIRE(dev == m->device, CTO_EINVAL, "%s: model lives on device %d but device %d is current (one process per GPU)", fn, m->device, dev);
+    return ensure_ws(m, B);
+}
+
+// cvt_forward between the events of the live kernel timing
+int cvt_forward_timed(cto_model* m, const float* x, int64_t B, float* logits, hipStream_t s, const RawIn* raw = nullptr) {
+    int rc;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (m->prof && (rc = prof_begin(m, s, &e0, &e1))) return rc;
-    rc = cvt_forward(m, x, B, logits, s);
+    if (m->prof && (rc = prof_begin(s, &e0, &e1))) return rc;
+    rc = cvt_forward(m, x, B, logits, s, raw);
     if (m->prof && rc == CTO_OK) {
         CTO_HIP(hipEventRecord(e1, s));
         m->prof_ev.emplace_back(e0, e1);
@@ -917,9 +917,8 @@ extern "C" int cto_model_forward(cto_model* m, const float* x, int64_t B, float*
     return rc;
 }
 
-namespace {
-// the fp32 tensor of the int16 one, for handles whose first layer has no int16 loader (split operands, the plain GRU schedule, an
-// embedding outside the block): float(double(v) * scale), the tensor kernel's own expression
+// the fp32 tensor of the int16 one, for handles whose first layer has no int16 loader (split operands, an embedding outside the
+// block): float(double(v) * scale), the tensor kernel's own expression
 __global__ __launch_bounds__(256) void k_expand_raw(const int16_t* __restrict__ raw, const int32_t* __restrict__ site_info, int which, int cov,
                                                     int64_t n, float* __restrict__ out) {
     const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -930,22 +929,19 @@ __global__ __launch_bounds__(256) void k_expand_raw(const int16_t* __restrict__ 
 }
 }  // namespace
 
+extern "C" int cto_model_forward(cto_model* m, const float* x, int64_t B, float* logits, void* stream) {
+    const int rc = forward_preamble("cto_model_forward", m, m && x && logits && B >= 0, B);
+    if (rc != CTO_OK || B == 0) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return m->kind == 1 ? bigru_forward(m, x, B, logits, s) : cvt_forward_timed(m, x, B, logits, s);
+}
+
 extern "C" int cto_model_forward_raw(cto_model* m, const int16_t* x_raw, const int32_t* site_info, int which, int min_rescale_cov, int64_t B,
                                      float* logits, void* stream) {
-    CTO_REQUIRE(m && x_raw && site_info && logits && B >= 0 && (which == 0 || which == 1), CTO_EINVAL, "cto_model_forward_raw: bad argument");
-    CTO_REQUIRE(B * 33 < (int64_t(1) << 31) / 640, CTO_EUNSUPPORTED, "batch too large for 32-bit row indices; split it");
-    if (B == 0) return CTO_OK;
-    {
-        int dev = -1;
-        CTO_HIP(hipGetDevice(&dev));
-        CTO_REQUIRE(dev == m->device, CTO_EINVAL, "cto_model_forward_raw: model lives on device %d but device %d is current (one process per GPU)",
-                    m->device, dev);
-    }
-    int rc = ensure_ws(m, B);
-    if (rc != CTO_OK) return rc;
+    const int rc = forward_preamble("cto_model_forward_raw", m, m && x_raw && site_info && logits && B >= 0 && (which == 0 || which == 1), B);
+    if (rc != CTO_OK || B == 0) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool native = m->kind == 1 ? (!m->gw1_split && gru_layer1_takes_raw())
-                                     : (m->fuse_blocks && m->fuse_embed && can_fuse_embed(m->st[0]));
+    const bool native = m->kind == 1 ? !m->gw1_split : (m->fuse_blocks && m->fuse_embed && can_fuse_embed(m->st[0]));
     if (!native) {
         if (m->xexp_B < B) {
             if (m->b_xexp) (void)hipFree(m->b_xexp);
@@ -959,15 +955,7 @@ extern "C" int cto_model_forward_raw(cto_model* m, const int16_t* x_raw, const i
         return cto_model_forward(m, m->b_xexp, B, logits, stream);
     }
     const RawIn raw{x_raw, site_info, which, min_rescale_cov};
-    if (m->kind == 1) return bigru_forward(m, nullptr, B, logits, s, &raw);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (m->prof && (rc = prof_begin(m, s, &e0, &e1))) return rc;
-    rc = cvt_forward(m, nullptr, B, logits, s, &raw);
-    if (m->prof && rc == CTO_OK) {
-        CTO_HIP(hipEventRecord(e1, s));
-        m->prof_ev.emplace_back(e0, e1);
-    }
-    return rc;
+    return m->kind == 1 ? bigru_forward(m, nullptr, B, logits, s, &raw) : cvt_forward_timed(m, nullptr, B, logits, s, &raw);
 }
 
 extern "C" int cto_model_profile(cto_model* m, int enable) {

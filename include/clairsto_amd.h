@@ -340,7 +340,7 @@ int cto_model_forward(cto_model* m, const float* x, int64_t B, float* logits, vo
  * site_info dev [B][12] as cto_featurize_sites writes it (the depth of pass `which` = 0 AFF / 1 NEG at [1 + which]), min_rescale_cov as
  * given to the tensor kernel (<= 0: no rescale).  The first layer's loader converts - float(double(v) * min_rescale_cov / depth), the
  * tensor kernel's own expression, so the logits equal cto_model_forward's on the fp32 tensor bit for bit - and the fp32 tensor is
- * never written or read.  Handles whose first layer has no int16 loader (split operands, CTO_GRU_ROT=0) expand it once inside the call. */
+ * never written or read.  Handles whose first layer has no int16 loader (split operands) expand it once inside the call. */
 int cto_model_forward_raw(cto_model* m, const int16_t* x_raw, const int32_t* site_info, int which, int min_rescale_cov, int64_t B,
                           float* logits, void* stream);
 /* algorithmic multiply-accumulate count per site of this model (for roofline accounting). */
