@@ -832,6 +832,34 @@ int cto_aspcf_squares(const double* x, int64_t n, double* out);       /* pow(x, 
 int cto_running_median(const double* x, int64_t n, int k, double* out);
 int cto_exact_pcf(const double* y, int64_t n, int kmin, double gamma, double* yhat);
 
+/* ----------------------------------------------------------------------------------------------
+ * ASCAT grid (csrc/ascat.hip): the purity/ploidy fit of the Verdict chain (create_distance_matrix, src/verdict/run_ascat.py:31-60 of
+ * the reference).  The rules are listed at the top of csrc/ascat.hip and derived in DESIGN.md "ASCAT grid".
+ *
+ * cto_ascat_distance: the distance of every cell of a ploidy x purity grid over S segments.
+ *   u, w, cnt, wgt  per segment, fp64 on the host, computed by the caller with numpy in the reference's operand order:
+ *                   u = (baf - 1) * 2 ** (logr / gamma), w = baf * 2 ** (logr / gamma), cnt = the segment's probes,
+ *                   wgt = 0.05 where baf == 0.5, else 1.  NaN and infinities are allowed: a NaN term counts as 0, as in np.nansum.
+ *   psi, rho        the P ploidies and the R purities of the grid; no rho may be 0
+ *   where           0: the kernel; 1: the host code of this call (threads over cells); the same bits
+ *   d               fp64 on the host, P x R row-major: per cell nansum(((|t| * |t|) * cnt) * wgt), t = m - max(rint(m), 0), m = the
+ *                   allele of the smaller nansum of nA = ((rho - 1) - u * c) / rho and nB = ((rho - 1) + w * c) / rho (nB on a tie
+ *                   or a NaN), c = (1 - rho) * 2 + rho * psi.  Every nansum is numpy's pairwise sum, buffers of 8192 included.
+ *   stats           may be NULL.  kernel_ms: HIP-event time of the kernel.
+ * The kernel: eight lanes per cell, 32 cells per workgroup, the per-segment arrays in LDS up to CTO_ASCAT_LDS_SEGMENTS segments and
+ * read from global memory above; no atomics, and no sum whose order depends on the launch.  CTO_EINVAL for S, P or R below 1, a rho
+ * of 0, a null pointer or another `where`; CTO_EUNSUPPORTED above CTO_ASCAT_MAX_SEGMENTS segments or 2^28 cells; CTO_EHIP without a
+ * device unless where = 1.  Thread-safe (the device part is serialised).
+ *
+ * cto_ascat_sum: the sum rule alone, np.nansum of n contiguous fp64 values as both paths compute it; for tests.
+ * ---------------------------------------------------------------------------------------------- */
+#define CTO_ASCAT_LDS_SEGMENTS 2048
+#define CTO_ASCAT_MAX_SEGMENTS (1 << 24)
+typedef struct cto_ascat_stats { int64_t n_cells, n_segments, host_path; double kernel_ms; } cto_ascat_stats;
+int cto_ascat_distance(const double* u, const double* w, const double* cnt, const double* wgt, int64_t S, const double* psi, int64_t P,
+                       const double* rho, int64_t R, int where /* 0 device, 1 host */, double* d /* host, P x R */, cto_ascat_stats* stats);
+int cto_ascat_sum(const double* x, int64_t n, double* out);
+
 #ifdef __cplusplus
 }
 #endif
