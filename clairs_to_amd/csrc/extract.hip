@@ -68,6 +68,7 @@ __global__ __launch_bounds__(XLANES) void k_extract_candidates(
     __builtin_amdgcn_wave_barrier();
     unsigned long long all4 = 0, pure4 = 0;          // 16-bit counters: A C G T (a column holds at most 32 767 read-bases)
     uint32_t stars = 0, n_row = 0, n_ind = 0;        // reads that pass --min-MQ (the row is printed at all); read-bases carrying an indel
+    uint32_t n_pass = 0;                             // read-bases that pass --min-BQ too (what the row prints)
     const int base = int(my_off - run0);
     int max_n = my_n;
 #pragma unroll
@@ -77,6 +78,7 @@ __global__ __launch_bounds__(XLANES) void k_extract_candidates(
         const int bq = int((ent >> 6) & 127u), mq = int((ent >> 13) & 255u);
         n_row += mq >= min_mq ? 1u : 0u;
         if (mq >= min_mq && bq >= min_bq) {           // what samtools --min-MQ / --min-BQ leaves in the column
+            ++n_pass;
             const unsigned long long one = 1ull << (16u * (b & 3u));
             if (b < 8u) {                              // depth = bases + placeholders, summed at the end
                 all4 += one;                           // pileup_dict[base] counts indel carriers too (:111-113)
@@ -110,6 +112,8 @@ __global__ __launch_bounds__(XLANES) void k_extract_candidates(
         for (int k = 0; k < 4; ++k) { cn_all[k] = uint32_t(all4 >> (16 * k)) & 0xffffu; cn_pure[k] = uint32_t(pure4 >> (16 * k)) & 0xffffu; }
         const int ref = pk.col_ref[c] & 3;
         const bool ref_ok = (pk.col_ref[c] & 0x80) == 0;     // rows whose reference base is not ACGT are skipped (:329-331)
+        // a row whose read-bases all fail --min-BQ prints `*` for its bases, which the reference reads as one placeholder
+        if (n_row > 0u && n_pass == 0u) stars = 1u;
         const int depth = int(stars + cn_all[0] + cn_all[1] + cn_all[2] + cn_all[3]);
         const double den = depth > 0 ? double(depth) : 1.0;
         bool pass_snv = false, has_alt_base = false, pass_indel = false;
@@ -204,7 +208,7 @@ __global__ __launch_bounds__(64) void k_hybrid_info(XPack pk, const int32_t* __r
     const int k0 = pk.key_off[c], nk = pk.key_off[c + 1] - k0;
     if (select_indel)
         for (int g = 0; g < nk; ++g) { gcnt[k0 + g] = 0u; gfirst[k0 + g] = INT32_MAX; }
-    int cnt[6] = {0, 0, 0, 0, 0, 0}, first[6] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MAX, INT32_MAX, INT32_MAX}, depth = 0;
+    int cnt[6] = {0, 0, 0, 0, 0, 0}, first[6] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MAX, INT32_MAX, INT32_MAX}, depth = 0, n_pass = 0;
     const int64_t e0 = pk.col_off[c], e1 = pk.col_off[c + 1];
     for (int64_t e = e0; e < e1; ++e) {
         const uint32_t ent = pk.entries[e];
@@ -212,6 +216,7 @@ __global__ __launch_bounds__(64) void k_hybrid_info(XPack pk, const int32_t* __r
         const int bq = int((ent >> 6) & 127u), mq = int((ent >> 13) & 255u);
         if (mq < min_mq || bq < min_bq) continue;
         const int at = int(e - e0);
+        ++n_pass;
         if (b < 8u) { ++depth; ++cnt[b & 3u]; first[b & 3u] = min(first[b & 3u], at); }
         else if (b == 8u || b == 9u) ++depth;
         if (kind != 0u) {
@@ -220,6 +225,7 @@ __global__ __launch_bounds__(64) void k_hybrid_info(XPack pk, const int32_t* __r
             else { const int w = (pk.key_meta[k] & 3u) == 1u ? 4 : 5; ++cnt[w]; first[w] = min(first[w], at); }
         }
     }
+    if (n_pass == 0) depth = 1;                      // the row exists (flag 32) and prints `*` for its bases: one placeholder, as above
     r[0] = int32_t(c); r[1] = depth;
     for (int k = 0; k < 6; ++k) { r[2 + k] = cnt[k]; r[8 + k] = first[k]; }
     r[14] = k0; r[15] = int32_t(flags[c]);

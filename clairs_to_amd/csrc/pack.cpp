@@ -580,7 +580,8 @@ int cto::pack_from_mpileup_impl(const char* text, size_t len, const char* ref_se
 extern "C" int cto_pack_from_arrays(const cto_pack_view* v, const int64_t* key_str_off, const char* key_str, cto_pack** out) try {
     CTO_REQUIRE(v && out, CTO_EINVAL, "cto_pack_from_arrays: null argument");
     CTO_REQUIRE(v->n_cols >= 0 && v->n_entries >= 0 && v->n_keys >= 0, CTO_EINVAL, "negative sizes");
-    auto* p = new cto_pack();
+    std::unique_ptr<cto_pack> own(new cto_pack());
+    cto_pack* p = own.get();
     p->col_pos.assign(v->col_pos, v->col_pos + v->n_cols);
     p->col_ref.assign(v->col_ref, v->col_ref + v->n_cols);
     p->col_off.assign(v->col_off, v->col_off + v->n_cols + 1);
@@ -595,19 +596,23 @@ extern "C" int cto_pack_from_arrays(const cto_pack_view* v, const int64_t* key_s
     } else {
         p->key_str_off.assign(size_t(v->n_keys) + 1, 0);
     }
+    // the limits the kernels rely on (16-bit counters, 11-bit key ids), as the text and BAM producers enforce them
     for (int64_t c = 0; c < v->n_cols; ++c) {
-        if (p->col_off[size_t(c) + 1] - p->col_off[size_t(c)] > kMaxDepth) {
-            delete p;
-            cto::set_error("column depth > %d unsupported", kMaxDepth);
-            return CTO_EUNSUPPORTED;
-        }
-        if (c > 0 && p->col_pos[size_t(c)] <= p->col_pos[size_t(c) - 1]) {
-            delete p;
-            cto::set_error("col_pos must be strictly increasing");
-            return CTO_EINVAL;
+        const int64_t e0 = p->col_off[size_t(c)], e1 = p->col_off[size_t(c) + 1];
+        const int64_t k0 = p->key_off[size_t(c)], k1 = p->key_off[size_t(c) + 1];
+        CTO_REQUIRE(e0 >= 0 && e0 <= e1 && e1 <= v->n_entries, CTO_EINVAL, "col_off must be non-decreasing within the entries");
+        CTO_REQUIRE(k0 >= 0 && k0 <= k1 && k1 <= v->n_keys, CTO_EINVAL, "key_off must be non-decreasing within the keys");
+        CTO_REQUIRE(e1 - e0 <= kMaxDepth, CTO_EUNSUPPORTED, "column depth %lld > %d unsupported", (long long)(e1 - e0), kMaxDepth);
+        CTO_REQUIRE(k1 - k0 <= kMaxKeysPerCol, CTO_EUNSUPPORTED, "%lld distinct indel keys in one column, more than %d", (long long)(k1 - k0),
+                    kMaxKeysPerCol);
+        CTO_REQUIRE(c == 0 || p->col_pos[size_t(c)] > p->col_pos[size_t(c) - 1], CTO_EINVAL, "col_pos must be strictly increasing");
+        for (int64_t e = e0; e < e1; ++e) {
+            const uint32_t ent = p->entries[size_t(e)];
+            CTO_REQUIRE(((ent >> 4) & 3u) == 0u || int64_t(ent >> 21) < k1 - k0, CTO_EINVAL,
+                        "indel entry %lld names key %u of a column with %lld keys", (long long)e, unsigned(ent >> 21), (long long)(k1 - k0));
         }
     }
-    *out = p;
+    *out = own.release();
     return CTO_OK;
 } CTO_CATCH("cto_pack_from_arrays", int)
 

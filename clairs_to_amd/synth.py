@@ -5,7 +5,7 @@ There are no BAMs, no samtools and no network on either box, so the workload is 
     the GPU path consumes), for one chunk of candidate sites;
   * `mpileup_text()` - the equivalent `samtools mpileup --reverse-del --output-MQ --min-BQ q` text of a
     chunk, for the CPU paths and for round-trip tests of the text tokeniser.
-Distributions follow SURVEY.md 8(d): depth ~ Poisson(mean) clipped to [4, 200], strand Bernoulli(0.5), per
+Distributions follow SURVEY.md 8(d): depth ~ Poisson(mean) clipped to [4, 200] (`depth_max`), strand Bernoulli(0.5), per
 read-base match 0.97 / mismatch 0.01 / deletion placeholder 0.01 / insertion 0.004 / deletion 0.006 (lengths
 geometric, capped at 80 so a few exceed max_indel_length), BQ ~ round(N(28, 8)) in [1, 50], MQ = 60 w.p. 0.93
 else uniform 0..59, 0.1 % N in the reference, a fixed alternative allele with AF ~ U(0.05, 0.6) at each
@@ -32,8 +32,11 @@ class SynthChunk:
 
     def __init__(self, n_sites, seed=20260928, depth_mean=50.0, start=100000, spacing=250, max_indel_length=60,
                  p_mismatch=0.01, p_star=0.01, p_ins=0.004, p_del=0.006, bq_mean=28.0, bq_sd=8.0, n_rate=0.001,
-                 bq_model=None):
-        """bq_model: None -> round(N(bq_mean, bq_sd)) in [1, 50]; ("discrete", values, probs); ("uniform", lo, hi)."""
+                 bq_model=None, depth_max=200, depth=None):
+        """bq_model: None -> round(N(bq_mean, bq_sd)) in [1, 50]; ("discrete", values, probs); ("uniform", lo, hi).
+        depth_max: upper clip of the Poisson column depths (the generator's own 200; tests of deep columns raise it).
+        depth: explicit depth of every column instead of the drawn ones, a number or one value per column (x-16 .. x+17 of every
+        candidate, duplicates removed).  Neither consumes random numbers: the other draws of a seed stay what they are per read-base."""
         rng = np.random.default_rng(seed)
         self.max_indel_length = max_indel_length
         # candidate positions: sorted, mean distance `spacing`, minimum distance 1 (windows may overlap)
@@ -50,7 +53,9 @@ class SynthChunk:
         is_n = rng.random(n_cols) < n_rate
         self.col_ref_char = np.where(is_n, ord("N"), np.frombuffer(b"ACGT", dtype=np.uint8)[ref]).astype(np.uint8)
         self.col_ref = np.where(is_n, 0x80, ref).astype(np.uint8)   # evc_base_from: N -> A (code 0); bit 7 = raw base not ACGT
-        depth = np.clip(rng.poisson(depth_mean, size=n_cols), 4, 200).astype(np.int64)
+        drawn = np.clip(rng.poisson(depth_mean, size=n_cols), 4, depth_max).astype(np.int64)
+        depth = drawn if depth is None else np.broadcast_to(np.asarray(depth, dtype=np.int64), (n_cols,)).copy()
+        assert depth.min(initial=0) >= 0 and depth.max(initial=0) <= 32767, "a column holds at most 32 767 read-bases"
         self.col_off = np.concatenate([[0], np.cumsum(depth)]).astype(np.int64)
         n_ent = int(self.col_off[-1])
         col_of = np.repeat(np.arange(n_cols, dtype=np.int64), depth)
@@ -86,6 +91,18 @@ class SynthChunk:
             raise ValueError("unknown bq_model %r" % (bq_model,))
         assert bq.max(initial=0) < 128
         mq = np.where(rng.random(n_ent) < 0.93, 60, rng.integers(0, 60, size=n_ent)).astype(np.uint32)
+        kid = self._index_keys(col_of, code, ilen, ivar, n_cols)
+        self.entries = (code | (kind << 4) | (bq << 6) | (mq << 13) | (kid << 21)).astype(np.uint32)
+        # over-long indels keep their length so the text writer can print them
+        self._ilen = ilen.astype(np.int32)
+        self._ivar = ivar.astype(np.int32)
+        self.n_sites = n_sites
+
+    def _index_keys(self, col_of, code, ilen, ivar, n_cols):
+        """The key tables (key_off, key_len, key_var, key_meta, key_group) of the read-bases whose `_okind` is set, and every
+        read-base's key id within its column."""
+        max_indel_length = self.max_indel_length
+        n_ent = col_of.size
         # ---- distinct indel keys per column, ids in first-seen order ----
         # (over-long indels keep a key: tensor creation ignores them, candidate extraction does not)
         okind = self._okind.astype(np.int64)
@@ -124,11 +141,7 @@ class SynthChunk:
         goff = np.searchsorted(gcol, np.arange(n_cols + 1))
         self.key_group = (grank[ginv] - goff[key_col]).astype(np.int32)
         assert n_keys == 0 or kid.max() < 2048
-        self.entries = (code | (kind << 4) | (bq << 6) | (mq << 13) | (kid << 21)).astype(np.uint32)
-        # over-long indels keep their length so the text writer can print them
-        self._ilen = ilen.astype(np.int32)
-        self._ivar = ivar.astype(np.int32)
-        self.n_sites = n_sites
+        return kid
 
     @classmethod
     def for_platform(cls, platform, n_sites, seed=None, **kw):

@@ -174,7 +174,9 @@ int   cto_tokenise_device(cto_dev_tokeniser* ctx, const char* text, size_t len, 
 /* test / tool aid: n bytes of device memory to the host (synchronous hipMemcpy); no reference counterpart */
 int cto_device_read(const void* d_src, void* h_dst, size_t n);
 /* Build a pack from caller-made arrays (synthetic generators, BAM readers); key strings are the
- * alt_info keys ("IACG", "DACGT") concatenated, key_str_off[n_keys+1]. Arrays are copied. */
+ * alt_info keys ("IACG", "DACGT") concatenated, key_str_off[n_keys+1]. Arrays are copied.  The limits of the text and BAM producers
+ * hold here too: a column of more than 32 767 read-bases or 2 048 keys is CTO_EUNSUPPORTED; offsets that leave their arrays or run
+ * backwards and an indel entry whose key id is not below its column's key count are CTO_EINVAL. */
 int cto_pack_from_arrays(const cto_pack_view* host_view, const int64_t* key_str_off,
                          const char* key_str, cto_pack** out);
 int cto_pack_view_of(const cto_pack* p, cto_pack_view* host_view);

@@ -658,7 +658,10 @@ def test_one_kernel_featurisation_equals_the_two_stage_path(dev, case):
               overlapping=dict(n=400, spacing=40, p_ins=0.03, p_del=0.03, depth_mean=50.0),
               deep=dict(n=40, spacing=40, p_ins=0.02, p_del=0.02, depth_mean=600.0),
               gaps=dict(n=200, spacing=40, p_ins=0.02, p_del=0.02, depth_mean=40.0))[case]
-    chunk = SynthChunk(kw["n"], seed=77, spacing=kw["spacing"], p_ins=kw["p_ins"], p_del=kw["p_del"], depth_mean=kw["depth_mean"])
+    chunk = SynthChunk(kw["n"], seed=77, spacing=kw["spacing"], p_ins=kw["p_ins"], p_del=kw["p_del"], depth_mean=kw["depth_mean"],
+                       depth_max=1000 if case == "deep" else 200)
+    if case == "deep":
+        assert np.diff(chunk.col_off).max() > 400
     dp = DevicePack(chunk.arrays(), dev)
     sites = chunk.site_pos.astype(np.int64)
     if case == "overlapping":
