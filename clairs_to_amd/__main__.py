@@ -3,6 +3,7 @@ hot-path sub-modules this package replaces and the post-calling steps it mirrors
 postfilter_variants -> postprocess_vcf); each takes the argv run_clairs_to builds for its namesake (tests/test_cli_argv.py).
 allele_counter takes alleleCounter's own options (the first command of the Verdict step, src/cna_germline_tagging.py:56-71).
 get_logr_and_baf and predict_germline_genotypes are steps 2 and 4 of that chain (:92-127): allele counts -> BAF -> germline genotypes;
+correct_logr is step 3 (:167-197): the logR corrected for GC content and replication timing, the table the later steps are handed;
 aspcf is its segmentation step (:130-140): logR, BAF and genotypes -> segmented logR and BAF; run_ascat (:143-164) turns those into the
 tumour's purity, ploidy and copy-number segments."""
 import importlib
@@ -10,7 +11,8 @@ import sys
 
 SUBMODULES = ("extract_candidates_calling", "concat_files", "create_tensor_pileup_calling", "predict", "call_variants", "pileup_call", "call_chunks",
               "sort_vcf", "postprocess_vcf", "haplotype_filtering", "realign_reads", "realign_variants",
-              "nonsomatic_tagging", "postfilter_variants", "allele_counter", "get_logr_and_baf", "predict_germline_genotypes", "aspcf", "run_ascat")
+              "nonsomatic_tagging", "postfilter_variants", "allele_counter", "get_logr_and_baf", "predict_germline_genotypes", "aspcf", "run_ascat",
+              "correct_logr")
 
 
 def dispatch(name, argv):

@@ -97,6 +97,11 @@ class AscatStats(C.Structure):
     _fields_ = [("n_cells", c_i64), ("n_segments", c_i64), ("host_path", c_i64), ("kernel_ms", C.c_double)]
 
 
+class CorrectLogrStats(C.Structure):
+    _fields_ = [("n_rows", c_i64), ("n_gc", c_i64), ("n_rt", c_i64), ("col_insert", c_i64), ("col_amplic", c_i64), ("col_replic", c_i64),
+                ("host_path", c_i64), ("kernel_ms", C.c_double)]
+
+
 class RunStats(C.Structure):
     _fields_ = [("candidates", c_i64), ("sites", c_i64), ("rows", c_i64), ("low_coverage", c_i64), ("clamped", c_i64), ("seconds", C.c_double),
                 ("produce_s", C.c_double), ("finish_s", C.c_double), ("launch_s", C.c_double), ("launcher_wait_s", C.c_double),
@@ -210,6 +215,8 @@ SYMBOLS = {
     "cto_exact_pcf": (C.c_int, [c_vp, c_i64, C.c_int, C.c_double, c_vp]),
     "cto_ascat_distance": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, C.c_int, c_vp, C.POINTER(AscatStats)]),
     "cto_ascat_sum": (C.c_int, [c_vp, c_i64, c_vp]),
+    "cto_correct_logr": (C.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, C.c_int, c_vp, c_vp, c_vp, C.POINTER(CorrectLogrStats)]),
+    "cto_correct_logr_basis": (C.c_int, [c_vp, c_i64, C.c_double, C.c_double, c_vp]),
 }
 
 for _name, (_res, _args) in SYMBOLS.items():

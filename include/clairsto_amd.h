@@ -862,6 +862,36 @@ int cto_ascat_distance(const double* u, const double* w, const double* cnt, cons
                        const double* rho, int64_t R, int where /* 0 device, 1 host */, double* d /* host, P x R */, cto_ascat_stats* stats);
 int cto_ascat_sum(const double* x, int64_t n, double* out);
 
+/* ----------------------------------------------------------------------------------------------
+ * logR correction (csrc/correctlogr.hip): step 3 of the Verdict chain (src/verdict/correct_logr.py of the reference).  The rules are
+ * listed at the top of csrc/correctlogr.hip and derived in DESIGN.md "logR correction".
+ *
+ * cto_correct_logr: the logR of N probes regressed on cubic B-splines of two GC-content columns and one replication-timing column.
+ *   logr, gc, rt    fp64 on the host: N values, N x G and N x T row-major, the rows in the order of the logR table
+ *   where           0: the kernels; 1: the host code of this call; the same bits
+ *   corr_gc         G values: |row 0 of np.corrcoef(gc, logr, rowvar=False)| without its first entry - GC column 0 against GC columns
+ *                   1 .. G - 1 and then against the logR; NaN where a column is constant.  corr_rt: the same of rt, T values.
+ *   residual        N values: y minus the least-squares fit of y on an intercept and the five B-splines of each chosen column
+ *   stats           may be NULL.  col_insert = argmax(corr_gc[:6]), col_amplic = argmax(corr_gc[7:12]) + 7, col_replic =
+ *                   argmax(corr_rt), the first NaN winning as in np.argmax; they index gc / rt directly.  kernel_ms: HIP-event time
+ *                   of the kernels, the copies left out.
+ * Every sum over rows is a fixed tree over blocks of CTO_CORRECT_LOGR_BLOCK_ROWS rows, the same for every launch and on the host; no
+ * floating-point atomics.  CTO_EINVAL for N < 2, G < 8, T < 1, a value that is not finite, a chosen column that is constant, a Cholesky
+ * pivot that is not positive (a chosen column with no value in one half of its range), a null pointer or another `where`;
+ * CTO_EUNSUPPORTED above CTO_CORRECT_LOGR_MAX_ROWS rows or CTO_CORRECT_LOGR_MAX_COLUMNS columns; CTO_EHIP without a device unless
+ * where = 1.  Thread-safe (the device part is serialised).
+ *
+ * cto_correct_logr_basis: the basis rule alone, the five B-splines of n values on the knots of [lo, hi] (n x 5, row-major); for tests.
+ * ---------------------------------------------------------------------------------------------- */
+#define CTO_CORRECT_LOGR_BLOCK_ROWS 256
+#define CTO_CORRECT_LOGR_MAX_COLUMNS 256
+#define CTO_CORRECT_LOGR_MAX_ROWS (1 << 28)
+typedef struct cto_correct_logr_stats { int64_t n_rows, n_gc, n_rt, col_insert, col_amplic, col_replic, host_path; double kernel_ms; } cto_correct_logr_stats;
+int cto_correct_logr(const double* logr, int64_t N, const double* gc /* N x G */, int64_t G, const double* rt /* N x T */, int64_t T,
+                     int where /* 0 device, 1 host */, double* corr_gc /* G */, double* corr_rt /* T */, double* residual /* N */,
+                     cto_correct_logr_stats* stats);
+int cto_correct_logr_basis(const double* x, int64_t n, double lo, double hi, double* out /* n x 5 */);
+
 #ifdef __cplusplus
 }
 #endif
