@@ -5,14 +5,16 @@ allele_counter takes alleleCounter's own options (the first command of the Verdi
 get_logr_and_baf and predict_germline_genotypes are steps 2 and 4 of that chain (:92-127): allele counts -> BAF -> germline genotypes;
 correct_logr is step 3 (:167-197): the logR corrected for GC content and replication timing, the table the later steps are handed;
 aspcf is its segmentation step (:130-140): logR, BAF and genotypes -> segmented logR and BAF; run_ascat (:143-164) turns those into the
-tumour's purity, ploidy and copy-number segments."""
+tumour's purity, ploidy and copy-number segments; tag_germline_variant (:157-164) is the last step: the exact binomial tests that set
+germline-looking PASS calls to LowQual and append the Verdict_* tags.  cna_germline_tagging is that chain's driver as run_clairs_to
+starts it: the seven steps, in this process."""
 import importlib
 import sys
 
 SUBMODULES = ("extract_candidates_calling", "concat_files", "create_tensor_pileup_calling", "predict", "call_variants", "pileup_call", "call_chunks",
               "sort_vcf", "postprocess_vcf", "haplotype_filtering", "realign_reads", "realign_variants",
               "nonsomatic_tagging", "postfilter_variants", "allele_counter", "get_logr_and_baf", "predict_germline_genotypes", "aspcf", "run_ascat",
-              "correct_logr")
+              "correct_logr", "tag_germline_variant", "cna_germline_tagging")
 
 
 def dispatch(name, argv):

@@ -102,6 +102,10 @@ class CorrectLogrStats(C.Structure):
                 ("host_path", c_i64), ("kernel_ms", C.c_double)]
 
 
+class TagGermlineStats(C.Structure):
+    _fields_ = [("n_calls", c_i64), ("n_with_segment", c_i64), ("n_tests", c_i64), ("host_path", c_i64), ("kernel_ms", C.c_double)]
+
+
 class RunStats(C.Structure):
     _fields_ = [("candidates", c_i64), ("sites", c_i64), ("rows", c_i64), ("low_coverage", c_i64), ("clamped", c_i64), ("seconds", C.c_double),
                 ("produce_s", C.c_double), ("finish_s", C.c_double), ("launch_s", C.c_double), ("launcher_wait_s", C.c_double),
@@ -217,6 +221,9 @@ SYMBOLS = {
     "cto_ascat_sum": (C.c_int, [c_vp, c_i64, c_vp]),
     "cto_correct_logr": (C.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, C.c_int, c_vp, c_vp, c_vp, C.POINTER(CorrectLogrStats)]),
     "cto_correct_logr_basis": (C.c_int, [c_vp, c_i64, C.c_double, C.c_double, c_vp]),
+    "cto_tag_germline": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, C.c_double, C.c_int, c_vp, c_vp, c_vp,
+                                   C.POINTER(TagGermlineStats)]),
+    "cto_binom_two_sided": (C.c_int, [c_vp, c_vp, c_vp, c_i64, C.c_int, c_vp]),
 }
 
 for _name, (_res, _args) in SYMBOLS.items():

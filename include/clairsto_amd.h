@@ -892,6 +892,39 @@ int cto_correct_logr(const double* logr, int64_t N, const double* gc /* N x G */
                      cto_correct_logr_stats* stats);
 int cto_correct_logr_basis(const double* x, int64_t n, double lo, double hi, double* out /* n x 5 */);
 
+/* ----------------------------------------------------------------------------------------------
+ * Germline tagging (csrc/taggermline.hip): the last step of the Verdict chain (src/verdict/tag_germline_variant.py:78-111 of the
+ * reference).  The rules are listed at the top of csrc/taggermline.hip and derived in DESIGN.md "Germline tagging".
+ *
+ * cto_tag_germline: per call the first segment that holds it, the expected allele fractions and the binomial tests against them.
+ *   ctg, pos, depth, freq   per call, on the host: the contig's id (interned by the caller), the position, the depth n, the AF
+ *   seg_*                   the S rows of the copy-number table in file order: contig id, start, end, nMajor, nMinor
+ *   purity                  the tumour's purity
+ *   where                   0: the kernel; 1: the host code of this call (threads over calls); the same bits
+ *   seg                     per call the smallest i with seg_chr[i] == ctg and seg_start[i] <= pos <= seg_end[i], or -1
+ *   af, pv                  per call four fp64 each, in the order G1, S1, G2, S2: the expected fractions and the two-sided p-values
+ *                           of rint(n * AF) successes in n trials; NaN where the reference has nan, and everywhere without a segment
+ *   stats                   may be NULL.  n_tests: p-values computed.  kernel_ms: HIP-event time of the kernel.
+ * The kernel: one wavefront per call, CTO_TAG_WAVES_PER_GROUP calls per workgroup, the table read from global memory (no LDS, so no
+ * limit below CTO_TAG_MAX_SEGMENTS); no atomics, and no sum or product whose order depends on the launch.  CTO_EINVAL, in scipy's
+ * words and with the call's index, for a call with a segment whose depth is below 1, whose rint(n * AF) is not within 0 .. n, or whose
+ * expected fraction is outside [0, 1]; CTO_EINVAL for a null pointer or another `where`; CTO_EUNSUPPORTED above CTO_TAG_MAX_CALLS calls,
+ * CTO_TAG_MAX_SEGMENTS segments or a depth of CTO_TAG_MAX_DEPTH; CTO_EHIP without a device unless where = 1.  Thread-safe (the device
+ * part is serialised).
+ *
+ * cto_binom_two_sided: the test rule alone on `count` triples (k, n, p), on either path, with the same error codes; for tests.
+ * ---------------------------------------------------------------------------------------------- */
+#define CTO_TAG_WAVES_PER_GROUP 4
+#define CTO_TAG_MAX_CALLS (1 << 26)
+#define CTO_TAG_MAX_SEGMENTS (1 << 24)
+#define CTO_TAG_MAX_DEPTH 2147483647
+typedef struct cto_tag_germline_stats { int64_t n_calls, n_with_segment, n_tests, host_path; double kernel_ms; } cto_tag_germline_stats;
+int cto_tag_germline(const int32_t* ctg, const int64_t* pos, const int64_t* depth, const double* freq, int64_t n_calls,
+                     const int32_t* seg_chr, const int64_t* seg_start, const int64_t* seg_end, const int64_t* seg_nmaj,
+                     const int64_t* seg_nmin, int64_t S, double purity, int where /* 0 device, 1 host */, int32_t* seg /* n_calls */,
+                     double* af /* n_calls x 4 */, double* pv /* n_calls x 4 */, cto_tag_germline_stats* stats);
+int cto_binom_two_sided(const int64_t* k, const int64_t* n, const double* p, int64_t count, int where /* 0 device, 1 host */, double* out);
+
 #ifdef __cplusplus
 }
 #endif
