@@ -7,14 +7,15 @@ correct_logr is step 3 (:167-197): the logR corrected for GC content and replica
 aspcf is its segmentation step (:130-140): logR, BAF and genotypes -> segmented logR and BAF; run_ascat (:143-164) turns those into the
 tumour's purity, ploidy and copy-number segments; tag_germline_variant (:157-164) is the last step: the exact binomial tests that set
 germline-looking PASS calls to LowQual and append the Verdict_* tags.  cna_germline_tagging is that chain's driver as run_clairs_to
-starts it: the seven steps, in this process."""
+starts it: the seven steps, in this process.  cal_af_distribution is the reference's src/cal_af_distribution.py, the AF half of its
+compare_vcf step: per truth variant the depth, ALT count and haplotype counts the tumour BAM shows, one pass over the BAM."""
 import importlib
 import sys
 
 SUBMODULES = ("extract_candidates_calling", "concat_files", "create_tensor_pileup_calling", "predict", "call_variants", "pileup_call", "call_chunks",
               "sort_vcf", "postprocess_vcf", "haplotype_filtering", "realign_reads", "realign_variants",
               "nonsomatic_tagging", "postfilter_variants", "allele_counter", "get_logr_and_baf", "predict_germline_genotypes", "aspcf", "run_ascat",
-              "correct_logr", "tag_germline_variant", "cna_germline_tagging")
+              "correct_logr", "tag_germline_variant", "cna_germline_tagging", "cal_af_distribution")
 
 
 def dispatch(name, argv):

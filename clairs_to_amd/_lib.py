@@ -85,6 +85,11 @@ class AlleleStats(C.Structure):
                 ("ms_inflate", C.c_double), ("ms_records", C.c_double), ("ms_count", C.c_double)]
 
 
+class AfStats(C.Structure):
+    _fields_ = [("n_chunks", c_i64), ("n_reads_entered", c_i64), ("n_blocks", c_i64), ("inflated_bytes", c_i64), ("fallback_chunks", c_i64),
+                ("host_loci", c_i64), ("ms_inflate", C.c_double), ("ms_records", C.c_double), ("ms_count", C.c_double)]
+
+
 class GermlineStats(C.Structure):
     _fields_ = [("n_runs", c_i64), ("n_probes", c_i64), ("host_path", c_i64), ("kernel_ms", C.c_double)]
 
@@ -212,6 +217,8 @@ SYMBOLS = {
     "cto_posterior_from_probs": (C.c_int, [c_vp, C.c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "cto_allele_counts": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, c_vp, c_i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_vp,
                                     c_vp, C.POINTER(AlleleStats)]),
+    "cto_af_tallies": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_int, C.c_int,
+                                 C.c_int, C.c_int, c_vp, c_vp, C.POINTER(AfStats)]),
     "cto_germline_window_dist": (C.c_int, [c_vp, c_vp, c_i64, C.c_int, C.c_int, c_vp, C.POINTER(GermlineStats)]),
     "cto_aspcf_windows": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, C.c_int, C.c_double, C.c_int, c_vp, c_vp, C.POINTER(AspcfStats)]),
     "cto_aspcf_squares": (C.c_int, [c_vp, c_i64, c_vp]),

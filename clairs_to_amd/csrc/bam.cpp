@@ -597,6 +597,115 @@ int allele_plan_chunks(const char* bam_path, const char* bai_path, const char* c
     return CTO_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ AF tallies, host path
+// The plain definition of the AF-tally rules (listed in full at the top of csrc/aftally.hip, which holds the C entry point and the
+// device path that is held equal to this one).  Every read that overlaps ctg:first-last selected locus is read through the index and
+// filtered as the column pile-up above filters; the reads are then walked in file order, so that per locus
+//   cover    counts the entered reads over it, reference skips included - the reads behind the first max_depth are not looked at;
+//   depth    counts the entries (an aligned base with its indel suffix, or the `*` of a deletion);
+//   the HP values of the covers queue up and entry i takes the i-th of them, as zip(base_list, hp_values) pairs them.
+int af_tallies_host_range(const char* bam_path, const char* bai_path, const char* ctg_name, const AfLoci& L, const int64_t* sel, int64_t n_sel,
+                          const AfParams& pr, int32_t* out, int64_t* n_entered, double* ms_records, double* ms_count) {
+    const double t0 = now();
+    if (n_entered) *n_entered = 0;
+    if (n_sel <= 0) return CTO_OK;
+    std::vector<int32_t> pos(static_cast<size_t>(n_sel));           // 1-based, ascending
+    for (int64_t i = 0; i < n_sel; ++i) {
+        pos[size_t(i)] = L.pos[sel[i]];
+        memset(out + sel[i] * 8, 0, 8 * sizeof(int32_t));
+    }
+    BamRegion rg;
+    CTO_REQUIRE(rg.open("cto_af_tallies", bam_path, bai_path, ctg_name, int64_t(pos.front()) - 1, pos.back(), false, false), CTO_EINVAL, "%s",
+                rg.err.c_str());
+    std::vector<int32_t> cover(size_t(n_sel), 0);
+    std::vector<std::vector<uint8_t>> hpq(pr.with_hp ? size_t(n_sel) : 0);      // HP classes of the covers no entry has taken yet
+    std::vector<uint32_t> hpq_head(pr.with_hp ? size_t(n_sel) : 0, 0);
+    int64_t entered = 0;
+    double t_count = 0.0;
+    for (BamRecord b;;) {
+        const int got = rg.next(&b);
+        CTO_REQUIRE(got >= 0, CTO_EINVAL, "%s", rg.err.c_str());
+        if (got == 0) break;
+        const int flag = b.flag;
+        if ((flag & pr.excl_flags) || (flag & 4) || b.mapq < pr.min_mq || b.n_cig == 0 || b.l_seq <= 0 || b.pos < 0) continue;
+        if ((flag & 1) && !(flag & 2)) continue;           // orphan (mpileup without -A)
+        CTO_REQUIRE(rg.lay_out(&b), CTO_EINVAL, "%s", rg.err.c_str());
+        const int enters = rg.enters(b);
+        CTO_REQUIRE(enters >= 0, CTO_EINVAL, "%s", rg.err.c_str());
+        if (!enters) continue;
+        ++entered;
+        const double tc0 = now();
+        int hp = 0;                                        // 0, 1, 2; 3 = the value 12, which the reference cannot index with
+        if (pr.with_hp) {
+            const uint8_t* aux = b.aux;
+            long long val;
+            for (AuxField f; aux_next(&aux, b.end, &f);)
+                if (f.t0 == 'H' && f.t1 == 'P' && aux_int(f, &val)) { hp = val == 1 ? 1 : (val == 2 ? 2 : (val == 12 ? 3 : 0)); break; }
+        }
+        auto base4 = [&](int q) { return (b.sq[q >> 1] >> ((~q & 1) << 2)) & 15; };
+        int64_t li = std::lower_bound(pos.begin(), pos.end(), b.pos + 1) - pos.begin();
+        int32_t rp = b.pos, qp = 0;
+        for (int k = 0; k < b.n_ops && li < n_sel; ++k) {
+            const int len = int(b.op(k) >> 4), opc = int(b.op(k) & 15);
+            const bool cons_ref = consumes_ref(opc);
+            const bool cons_q = consumes_query(opc);
+            if (cons_ref) {
+                for (; li < n_sel && int64_t(pos[size_t(li)]) - 1 < int64_t(rp) + len; ++li) {
+                    const size_t i = size_t(li);
+                    const int64_t g = sel[li];
+                    int32_t* o = out + g * 8;
+                    if (pr.max_depth > 0 && cover[i] >= pr.max_depth) continue;
+                    ++cover[i];
+                    if (pr.with_hp) hpq[i].push_back(uint8_t(hp));
+                    if (opc == 3) continue;                // N: an HP value, no entry
+                    bool match = false;
+                    if (opc != 2) {                        // an aligned base; D is the entry `*`, which no allele equals
+                        const int off = pos[i] - 1 - rp, q = qp + off;
+                        const int c = base4(q);
+                        const char letter = c == 1 ? 'A' : (c == 2 ? 'C' : (c == 4 ? 'G' : (c == 8 ? 'T' : 'N')));
+                        int suffix = 0, nlen = 0;          // 1: +SEQ, 2: -N..N
+                        if (off == len - 1) {
+                            int nx = k + 1;
+                            while (nx < b.n_ops && (b.op(nx) & 15) == 6) ++nx;      // P
+                            if (nx < b.n_ops && ((b.op(nx) & 15) == 1 || (b.op(nx) & 15) == 2)) { suffix = int(b.op(nx) & 15); nlen = int(b.op(nx) >> 4); }
+                        }
+                        const int kind = L.kind[g];
+                        if (char(L.base[g]) == letter) {
+                            if (kind == 0) match = suffix == 0;
+                            else if (kind == 2) match = suffix == 2 && nlen == L.del_len[g];
+                            else if (kind == 1 && suffix == 1 && int64_t(nlen) == L.ins_off[g + 1] - L.ins_off[g]) {
+                                const char* want = L.ins_bytes + L.ins_off[g];
+                                match = true;
+                                for (int x = 0; x < nlen && match; ++x) {
+                                    char ib = kNt16[base4(q + 1 + x)];
+                                    if (ib == '=') ib = 'N';
+                                    match = ib == want[x];
+                                }
+                            }
+                        }
+                    }
+                    ++o[0];
+                    o[1] += match;
+                    if (pr.with_hp) {
+                        const int h = hpq[i][hpq_head[i]++];
+                        CTO_REQUIRE(h != 3, CTO_EINVAL, "cto_af_tallies: an entry at %s:%d is paired with HP:i:12, which the reference's HAP_LIST[int(hap)] cannot index "
+                                    "(src/cal_af_distribution.py:107 raises IndexError)", ctg_name, int(pos[i]));
+                        ++o[5 + h];
+                        o[2 + h] += match;
+                    }
+                }
+                rp += len;
+            }
+            if (cons_q) qp += len;
+        }
+        t_count += now() - tc0;
+    }
+    if (n_entered) *n_entered = entered;
+    if (ms_records) *ms_records = now() - t0 - t_count;
+    if (ms_count) *ms_count = t_count;
+    return CTO_OK;
+}
+
 }  // namespace cto
 
 // The byte range of the BAM that holds every BGZF block the index names for ctg:start-end (the block the last chunk ends in

@@ -146,4 +146,11 @@ int allele_counts_host_range(const char* bam_path, const char* bai_path, const c
                              const AlleleParams& pr, int32_t* counts, int64_t* n_entered, double* ms_records, double* ms_count);
 int allele_plan_chunks(const char* bam_path, const char* bai_path, const char* ctg_name, const int32_t* loci, int64_t n_loci, int64_t budget,
                        std::vector<int64_t>* cuts);
+// AF tallies (the C entry point, the rules and the device path: csrc/aftally.hip; the host rules: csrc/bam.cpp).  The arrays are the
+// call's own, over all its loci; sel[0 .. n_sel) are the ascending indices of the loci to tally, and row sel[i] of `out` (n_loci x 8,
+// zeroed for them by the call) receives the result.
+struct AfLoci { const int32_t* pos; const uint8_t *kind, *base; const int32_t* del_len; const char* ins_bytes; const int64_t* ins_off; };
+struct AfParams { int min_mq, excl_flags, max_depth, with_hp; };
+int af_tallies_host_range(const char* bam_path, const char* bai_path, const char* ctg_name, const AfLoci& loci, const int64_t* sel, int64_t n_sel,
+                          const AfParams& pr, int32_t* out, int64_t* n_entered, double* ms_records, double* ms_count);
 }  // namespace cto

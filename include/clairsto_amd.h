@@ -775,6 +775,38 @@ int cto_allele_counts(const char* bam_path, const char* bai_path, const char* ct
                       int32_t* counts /* n_loci x 4, host */, cto_allele_stats* stats);
 
 /* ----------------------------------------------------------------------------------------------
+ * AF tallies (csrc/aftally.hip, host rules in csrc/bam.cpp): per truth variant the depth, the ALT count and the per-haplotype counts that
+ * the reference's src/cal_af_distribution.py:44-115 reads off one `samtools mpileup --min-MQ 20 --min-BQ 0 --excl-flags 2316
+ * [--output-extra HP] -r ctg:pos-pos` row per variant - here one pass over the BAM for all loci of a contig.  PARITY UNPINNED against
+ * samtools (no htslib on the build or GPU machines); the rules and every unpinned point are listed at the top of csrc/aftally.hip.
+ *   loci        1-based positions on ctg_name, strictly ascending
+ *   kind/base   what an entry of the column has to be to count as ALT: 0 a plain base equal to `base` (SNV); 1 `base` followed by an
+ *               insertion of exactly the bytes ins_bytes[ins_off[i] .. ins_off[i + 1]) (upper-case ASCII); 2 `base` followed by a deletion
+ *               of del_len[i] bases; 3 nothing matches.  del_len, ins_bytes and ins_off are read only for the loci of their kind, but
+ *               ins_off has n_loci + 1 ascending entries.
+ *   max_depth   only the first max_depth entered reads that cover a locus are looked at, in file order (<= 0: no cap)
+ *   with_hp     0: out[2..7] stay 0; else the HP:i tag of every covering read is paired with the column's entries as the reference's zip
+ *               pairs them (a reference skip has an HP value and no entry, so it shifts the pairing).  An entry paired with HP 12 is the
+ *               reference's IndexError: CTO_EINVAL.
+ *   where       0: host (the plain definition, `host_threads` threads over chunks of loci); 1: device - the allele counter's chunking and
+ *               front end, one wave per entered read.  Loci whose result depends on the order of the reads (a covering reference skip
+ *               under with_hp, a cover above max_depth, a covering HP of 12) and insertion alleles longer than CTO_AF_MAX_INS bases are
+ *               recounted by the host path, locus by locus (host_loci); a damaged chunk is redone whole by it (fallback_chunks).
+ *   out         n_loci x 8 int32 on the host: depth, alt, h0 h1 h2 (ALT entries per haplotype), a0 a1 a2 (all entries per haplotype)
+ * CTO_AF_CHUNK_BYTES (environment, for tests): the budget of inflated bytes per chunk, as CTO_ALLELE_CHUNK_BYTES.
+ * ---------------------------------------------------------------------------------------------- */
+#define CTO_AF_MAX_INS 64
+typedef struct cto_af_stats { int64_t n_chunks, n_reads_entered, n_blocks, inflated_bytes, fallback_chunks, host_loci;
+                              double ms_inflate, ms_records, ms_count; } cto_af_stats;
+int cto_af_tallies(const char* bam_path, const char* bai_path, const char* ctg_name,
+                   const int32_t* loci /* 1-based, strictly ascending */, int64_t n_loci,
+                   const uint8_t* kind /* 0 SNV, 1 insertion, 2 deletion, 3 never matches */, const uint8_t* base /* anchor / ALT letter */,
+                   const int32_t* del_len, const char* ins_bytes, const int64_t* ins_off /* n_loci + 1 */,
+                   int min_mq, int excl_flags, int max_depth, int with_hp,
+                   int where /* 0 host, 1 device */, int host_threads, void* stream,
+                   int32_t* out /* n_loci x 8: depth, alt, h0 h1 h2, a0 a1 a2; host */, cto_af_stats* stats);
+
+/* ----------------------------------------------------------------------------------------------
  * Germline genotypes (csrc/germline.hip): the window distances of the reference's predictGermlineGenotypes
  * (src/verdict/predict_germline_genotypes.py:70-154, step 4 of the Verdict chain), over runs of undecided probes.
  *   c               the mirrored BAFs min(baf, 1 - baf) of the undecided probes, run after run, fp64 on the host; no NaN
