@@ -476,6 +476,13 @@ int cvt_forward(cto_model* m, const float* x, int64_t B, float* logits, hipStrea
                                   C, ACT_NONE)))
                 return rc;
             const size_t smem = size_t(st.w * st.inner + st.wkv * 2 * st.inner + st.heads * st.w * st.wkv) * sizeof(float);
+            // stage 1 (W = 17, WKV = 9) asks for 9 572 bytes per head: past the 64 KB a launch gets unasked from 7 heads on
+            static bool attr_set = false;
+            if (!attr_set) {
+                CTO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attention), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            int((17 * 512 + 9 * 1024 + 8 * 17 * 9) * sizeof(float))));
+                attr_set = true;
+            }
             hipLaunchKernelGGL(k_attention, dim3(unsigned(B)), dim3(256), smem, s, m->b_q, m->b_kv, m->b_o, st.w, st.wkv,
                                st.heads);
             CTO_HIP(hipGetLastError());
