@@ -8,14 +8,16 @@ aspcf is its segmentation step (:130-140): logR, BAF and genotypes -> segmented 
 tumour's purity, ploidy and copy-number segments; tag_germline_variant (:157-164) is the last step: the exact binomial tests that set
 germline-looking PASS calls to LowQual and append the Verdict_* tags.  cna_germline_tagging is that chain's driver as run_clairs_to
 starts it: the seven steps, in this process.  cal_af_distribution is the reference's src/cal_af_distribution.py, the AF half of its
-compare_vcf step: per truth variant the depth, ALT count and haplotype counts the tumour BAM shows, one pass over the BAM."""
+compare_vcf step: per truth variant the depth, ALT count and haplotype counts the tumour BAM shows, one pass over the BAM.  compare_vcf is the command the reference's quick demos end with (src/compare_vcf.py): the
+calls against a truth set -> precision, recall and F1, the classification and the cut-off sweeps on the GPU.
+    usage: python -m clairs_to_amd compare_vcf --truth_vcf_fn TRUTH --input_vcf_fn CALLS [--bed_fn BED] [--ctg_name CTG] [--output_dir DIR]"""
 import importlib
 import sys
 
 SUBMODULES = ("extract_candidates_calling", "concat_files", "create_tensor_pileup_calling", "predict", "call_variants", "pileup_call", "call_chunks",
               "sort_vcf", "postprocess_vcf", "haplotype_filtering", "realign_reads", "realign_variants",
               "nonsomatic_tagging", "postfilter_variants", "allele_counter", "get_logr_and_baf", "predict_germline_genotypes", "aspcf", "run_ascat",
-              "correct_logr", "tag_germline_variant", "cna_germline_tagging", "cal_af_distribution")
+              "correct_logr", "tag_germline_variant", "cna_germline_tagging", "cal_af_distribution", "compare_vcf")
 
 
 def dispatch(name, argv):

@@ -111,6 +111,18 @@ class TagGermlineStats(C.Structure):
     _fields_ = [("n_calls", c_i64), ("n_with_segment", c_i64), ("n_tests", c_i64), ("host_path", c_i64), ("kernel_ms", C.c_double)]
 
 
+class CompareStats(C.Structure):
+    _fields_ = [("n_input", c_i64), ("n_truth", c_i64), ("n_cutoffs", c_i64), ("host_path", c_i64), ("kernel_ms", C.c_double)]
+
+
+class CompareRecords(C.Structure):
+    _fields_ = [(name, c_vp) for name in ("ctg", "pos", "ref_len", "alt_len", "n_alt", "allele", "gt", "qual", "flags")] + [("n", c_i64)]
+
+
+class CompareBeds(C.Structure):
+    _fields_ = [("n_sets", c_i32), ("n_ctg", c_i32), ("named", c_vp), ("off", c_vp), ("start", c_vp), ("end", c_vp)]
+
+
 class RunStats(C.Structure):
     _fields_ = [("candidates", c_i64), ("sites", c_i64), ("rows", c_i64), ("low_coverage", c_i64), ("clamped", c_i64), ("seconds", C.c_double),
                 ("produce_s", C.c_double), ("finish_s", C.c_double), ("launch_s", C.c_double), ("launcher_wait_s", C.c_double),
@@ -231,6 +243,9 @@ SYMBOLS = {
     "cto_tag_germline": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, C.c_double, C.c_int, c_vp, c_vp, c_vp,
                                    C.POINTER(TagGermlineStats)]),
     "cto_binom_two_sided": (C.c_int, [c_vp, c_vp, c_vp, c_i64, C.c_int, c_vp]),
+    "cto_compare_calls": (C.c_int, [C.POINTER(CompareRecords), C.POINTER(CompareRecords), c_vp, c_vp, C.POINTER(CompareBeds), C.c_int, C.c_int, C.c_int,
+                                    C.c_int, c_vp, c_i64, c_vp, c_i64, C.c_int, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.POINTER(CompareStats)]),
+    "cto_compare_sweep": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, C.c_int, C.c_int, c_vp, c_vp]),
 }
 
 for _name, (_res, _args) in SYMBOLS.items():

@@ -33,18 +33,23 @@ def _default_where():
 
 
 class Variant(object):
-    """what cal_af reads of shared/utils.py:Position"""
-    __slots__ = ("ctg_name", "pos", "reference_bases", "alternate_bases", "row_str")
+    """what cal_af and compare_vcf read of shared/utils.py:Position"""
+    __slots__ = ("ctg_name", "pos", "reference_bases", "alternate_bases", "row_str", "genotype", "qual", "af")
 
-    def __init__(self, ctg_name, pos, ref_base, alt_base, row_str):
+    def __init__(self, ctg_name, pos, ref_base, alt_base, row_str, genotype=None, qual=None, af=None):
         self.ctg_name, self.pos, self.reference_bases, self.row_str = ctg_name, pos, ref_base, row_str
         self.alternate_bases = [alt_base] if "," not in alt_base else alt_base.split(",")
+        self.genotype, self.qual, self.af = genotype, qual, af
 
 
-def read_vcf(vcf_fn, ctg_name=None, filter_tag=None):
-    """shared/vcf.py:238-352, VcfReader(vcf_fn, ctg_name, show_ref=False, keep_row_str=True, filter_tag).read_vcf() -> variant_dict: key = POS
-    when ctg_name is one name, (CHROM, POS) otherwise; a repeated key keeps the last row; 0/0 rows are dropped, a genotype that does not
-    parse is kept; the `*` ALT rule of :312-320; plain or gzip input (the reference pipes every file through `gzip -fdc`)."""
+def read_vcf(vcf_fn, ctg_name=None, filter_tag=None, ctg_start=None, ctg_end=None, skip_genotype=False, keep_af=False, min_qual=None, max_qual=None,
+             discard_indel=False):
+    """shared/vcf.py:238-352, VcfReader(vcf_fn, ctg_name, show_ref=False, keep_row_str=True, filter_tag, ...).read_vcf() -> variant_dict: key = POS
+    when ctg_name is one name, (CHROM, POS) otherwise; a repeated key keeps its first place and its last row; 0/0 rows are dropped unless
+    skip_genotype, a genotype that does not parse is kept as [-1, -1]; the `*` ALT rule of :312-320; plain or gzip input (the reference pipes every
+    file through `gzip -fdc`).  compare_vcf's options: rows outside ctg_start .. ctg_end (both given) are dropped; discard_indel drops a row whose
+    REF or whole ALT string is longer than one letter (a multi-allelic SNV row too); min_qual / max_qual drop by float(QUAL), and a QUAL they
+    cannot parse becomes None; keep_af stores AF (or VAF) of column 10 by column 9's index, None without either."""
     out = OrderedDict()
     if vcf_fn is None or not os.path.exists(vcf_fn):
         return out
@@ -57,6 +62,7 @@ def read_vcf(vcf_fn, ctg_name=None, filter_tag=None):
     else:
         only, tuple_keys = frozenset([ctg_name]), False
     allowed = None if filter_tag is None else filter_tag.split(",")
+    in_region = ctg_start is not None and ctg_end is not None
     header_last_column = []
     with (gzip.open(vcf_fn, "rt") if gz else open(vcf_fn)) as fo:
         for row in fo:
@@ -68,10 +74,22 @@ def read_vcf(vcf_fn, ctg_name=None, filter_tag=None):
             chromosome, position = columns[0], columns[1]
             if only is not None and chromosome not in only:
                 continue
+            if in_region and not (ctg_start <= int(position) <= ctg_end):
+                continue
             flt = columns[6] if len(columns) >= 7 else None
             if allowed is not None and flt not in allowed:
                 continue
             reference, alternate = columns[3], columns[4]
+            if discard_indel and (len(reference) > 1 or len(alternate) > 1):
+                continue
+            try:
+                qual = columns[5] if len(columns) > 5 else None
+                if min_qual is not None and float(qual) < min_qual:
+                    continue
+                if max_qual is not None and float(qual) > max_qual:
+                    continue
+            except Exception:
+                qual = None
             last_column = columns[-2] if tumor_in_last else columns[-1]
             genotype = last_column.split(":")[0].replace("/", "|").replace(".", "0").split("|")
             try:
@@ -87,10 +105,15 @@ def read_vcf(vcf_fn, ctg_name=None, filter_tag=None):
                     g1, g2 = "0", "1"
             except Exception:
                 g1 = g2 = -1
+            af = None
+            if keep_af:
+                tag_list = columns[8].split(":")
+                if "AF" in tag_list or "VAF" in tag_list:
+                    af = float(columns[9].split(":")[tag_list.index("AF") if "AF" in tag_list else tag_list.index("VAF")])
             position = int(position)
-            if g1 == "0" and g2 == "0":
+            if g1 == "0" and g2 == "0" and not skip_genotype:
                 continue
-            out[(chromosome, position) if tuple_keys else position] = Variant(chromosome, position, reference, alternate, row)
+            out[(chromosome, position) if tuple_keys else position] = Variant(chromosome, position, reference, alternate, row, [int(g1), int(g2)], qual, af)
     return out
 
 

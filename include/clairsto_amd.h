@@ -957,6 +957,68 @@ int cto_tag_germline(const int32_t* ctg, const int64_t* pos, const int64_t* dept
                      double* af /* n_calls x 4 */, double* pv /* n_calls x 4 */, cto_tag_germline_stats* stats);
 int cto_binom_two_sided(const int64_t* k, const int64_t* n, const double* p, int64_t count, int where /* 0 device, 1 host */, double* out);
 
+/* ----------------------------------------------------------------------------------------------
+ * compare_vcf (csrc/comparevcf.hip): the reference's evaluation command (src/compare_vcf.py:82-538).  One call takes the parsed input
+ * calls and truth records, in dict order, and returns what the reference's four loops and its two cut-off sweeps produce.  The twelve
+ * rules are listed at the top of csrc/comparevcf.hip and derived in DESIGN.md "compare_vcf".
+ *
+ * cto_compare_calls
+ *   input, truth            the two record tables, on the host.  Per record: the contig's id (interned by the caller; with --ctg_name every
+ *                           record carries that contig's id), the 1-based position, len(REF), len(first ALT), the number of ALTs, an
+ *                           allele id (equal ids = equal (REF, first ALT) strings, interned by the caller over both tables), the genotype
+ *                           pair, QUAL (NaN for none; input only, may be NULL for the truth and without cut-offs) and a flag byte:
+ *                           CTO_CMP_HIGHCONF the row holds `PASS;HighConf`, CTO_CMP_H its INFO holds H, CTO_CMP_LOWAF the key is in
+ *                           the low-AF set.  The keys (contig id, pos) of a table are distinct, as a dict's are.
+ *   truth_sorted_keys       ((int64)contig id << 32 | (uint32)pos) of every truth record, ascending strictly; truth_order[k] is the record
+ *                           that key k belongs to.  The caller sorts.
+ *   beds                    n_sets interval sets over n_ctg contigs: set 0 is the FP BED, the others the stratification BEDs.  The
+ *                           intervals of set s on contig c are start/end[off[s * n_ctg + c] .. off[s * n_ctg + c + 1]), 0-based
+ *                           [start, end), sorted and merged (end[a - 1] <= start[a]); named[s] = the number of contigs the file named.
+ *   benchmark_indel, high_confident_only, skip_genotyping      the reference's switches, 0 or 1
+ *   validate_phase          0, or --validate_phase_only's 1 / 2: the input-record half of that gate (rule 4)
+ *   cutoffs, roc_cutoffs    two lists of QUAL cut-offs as doubles, each a superset of what the caller will read (it cannot know fp_set and
+ *                           tp_set before the call); a NaN cut-off counts nothing
+ *   where                   0: the kernels, on `stream` (the caller's); 1: the host code of this call on host_threads threads (0: up to 16)
+ *   input_sets              per input record CTO_CMP_FP | TP | FN | FP_FN | TRUTH (in that set) | KEPT (left in the dict by the input loop)
+ *   truth_sets              per truth record CTO_CMP_FN (in fn_set by the last loop) | KEPT (left in the dict by the truth loop)
+ *   counters                CTO_CMP_COUNTERS of them: tp_snv tp_ins tp_del fp_snv fp_ins fp_del fn_snv fn_ins fn_del gt_mismatch
+ *                           input_out_of_bed truth_out_of_bed input_out_of_strat_bed truth_out_of_strat_bed len(input dict) len(truth dict)
+ *   sweep, roc_sweep        per cut-off two counts: the fp_set records, the tp_set records with QUAL >= the cut-off
+ *   stats                   may be NULL.  n_cutoffs: both lists.  kernel_ms: HIP-event time from the first kernel to the last.
+ * Every output is an integer and no sum depends on an order: the two paths return the same values.  CTO_EINVAL for a null pointer, a
+ * contig id outside 0 .. n_ctg - 1, sorted keys that do not ascend or do not name their records, intervals that are empty, unsorted or
+ * overlap, more than CTO_CMP_MAX_SETS sets, CTO_CMP_MAX_RECORDS records or intervals, CTO_CMP_MAX_CUTOFFS cut-offs; CTO_EHIP without a
+ * device unless where = 1.  Thread-safe (the device part is serialised).
+ *
+ * cto_compare_sweep: rule 12 alone on `n` values, each with CTO_CMP_FP and / or CTO_CMP_TP in `sets`; out[2k], out[2k + 1]; for tests.
+ * ---------------------------------------------------------------------------------------------- */
+#define CTO_CMP_HIGHCONF 1
+#define CTO_CMP_H 2
+#define CTO_CMP_LOWAF 4
+#define CTO_CMP_FP 1
+#define CTO_CMP_TP 2
+#define CTO_CMP_FN 4
+#define CTO_CMP_FP_FN 8
+#define CTO_CMP_TRUTH 16
+#define CTO_CMP_KEPT 32
+#define CTO_CMP_COUNTERS 16
+#define CTO_CMP_MAX_SETS 30
+#define CTO_CMP_MAX_RECORDS (1 << 27)
+#define CTO_CMP_MAX_CUTOFFS (1 << 24)
+typedef struct cto_compare_records { const int32_t *ctg, *pos, *ref_len, *alt_len, *n_alt, *allele, *gt /* n x 2 */; const double* qual;
+                                     const uint8_t* flags; int64_t n; } cto_compare_records;
+typedef struct cto_compare_beds { int32_t n_sets, n_ctg; const int32_t* named /* n_sets */; const int64_t* off /* n_sets x n_ctg + 1 */;
+                                  const int64_t *start, *end; } cto_compare_beds;
+typedef struct cto_compare_stats { int64_t n_input, n_truth, n_cutoffs, host_path; double kernel_ms; } cto_compare_stats;
+int cto_compare_calls(const cto_compare_records* input, const cto_compare_records* truth, const int64_t* truth_sorted_keys,
+                      const int32_t* truth_order, const cto_compare_beds* beds, int benchmark_indel, int high_confident_only,
+                      int skip_genotyping, int validate_phase, const double* cutoffs, int64_t n_cutoffs, const double* roc_cutoffs,
+                      int64_t n_roc, int where /* 0 device, 1 host */, int host_threads, void* stream, uint8_t* input_sets /* input->n */,
+                      uint8_t* truth_sets /* truth->n */, int64_t* counters /* CTO_CMP_COUNTERS */, int64_t* sweep /* n_cutoffs x 2 */,
+                      int64_t* roc_sweep /* n_roc x 2 */, cto_compare_stats* stats);
+int cto_compare_sweep(const double* values, const uint8_t* sets, int64_t n, const double* cutoffs, int64_t n_cutoffs,
+                      int where /* 0 device, 1 host */, int host_threads, void* stream, int64_t* out /* n_cutoffs x 2 */);
+
 #ifdef __cplusplus
 }
 #endif
