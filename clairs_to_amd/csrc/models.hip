@@ -965,6 +965,20 @@ extern "C" int cto_model_forward_raw(cto_model* m, const int16_t* x_raw, const i
     return m->kind == 1 ? bigru_forward(m, nullptr, B, logits, s, &raw) : cvt_forward_timed(m, nullptr, B, logits, s, &raw);
 }
 
+// Test aid, read-only: what the last BiGRU forward of B sites left in the workspace - layer 1's output and the fc1 partial slabs of
+// the fused layer-2 kernel (k_head only reads them) - copied device to device on `stream`.  Either destination may be null.
+extern "C" int cto_debug_bigru_layers(cto_model* m, int64_t B, float* h1_out, float* slab_out, void* stream) {
+    CTO_REQUIRE(m && B >= 0, CTO_EINVAL, "cto_debug_bigru_layers: bad argument");
+    CTO_REQUIRE(m->kind == 1, CTO_EINVAL, "cto_debug_bigru_layers: not a BiGRU handle");
+    CTO_REQUIRE(B <= m->ws_B, CTO_EINVAL, "cto_debug_bigru_layers: B = %lld but the workspace holds %lld sites", (long long)B, (long long)m->ws_B);
+    if (B == 0) return CTO_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (h1_out) CTO_HIP(hipMemcpyAsync(h1_out, m->b_h, size_t(B) * 33 * 256 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    // the forward of B sites wrote the slabs B * 128 floats apart, whatever the workspace holds
+    if (slab_out) CTO_HIP(hipMemcpyAsync(slab_out, m->b_slab, size_t(B) * 2 * 128 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return CTO_OK;
+}
+
 extern "C" int cto_model_profile(cto_model* m, int enable) {
     CTO_REQUIRE(m, CTO_EINVAL, "cto_model_profile: null model");
     m->prof = enable != 0;

@@ -345,6 +345,10 @@ int cto_model_forward(cto_model* m, const float* x, int64_t B, float* logits, vo
  * never written or read.  Handles whose first layer has no int16 loader (split operands) expand it once inside the call. */
 int cto_model_forward_raw(cto_model* m, const int16_t* x_raw, const int32_t* site_info, int which, int min_rescale_cov, int64_t B,
                           float* logits, void* stream);
+/* Test aid, read-only: after a forward of exactly B sites on a BiGRU handle, copies (device to device, on `stream`) layer 1's output
+ * [B][33][256] (directions concatenated) into h1_out and the two fc1 partial sums of the fused layer-2 kernel [2][B][128] (one per
+ * direction, no bias) into slab_out.  Either pointer may be null.  CTO_EINVAL for a CvT handle or a B the workspace never held. */
+int cto_debug_bigru_layers(cto_model* m, int64_t B, float* h1_out, float* slab_out, void* stream);
 /* algorithmic multiply-accumulate count per site of this model (for roofline accounting). */
 int64_t cto_model_macs_per_site(const cto_model* m);
 int  cto_model_n_out(const cto_model* m);

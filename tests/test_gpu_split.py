@@ -59,8 +59,10 @@ def _neg_logits(eng, x_neg, B, K, dev):
 @pytest.mark.parametrize("K", [4, 6])
 def test_split_kernel_against_the_oracle_and_the_f32_kernel(dev, oracle_lib, kind, tol_logit, K):
     """(a) 160 sites against the oracle: NEG logits within tol_logit (the fp32 kernel sits at ~4e-6, f16 at ~6e-6, bf16 at ~2e-5),
-    probabilities within the path's 1e-4, every decision equal; (b) a full 4096-site chunk and ragged batches (1, 15, 16, 17, 33,
-    1000: whole and partial 32- and 16-site tiles, both launch ranges) against the fp32 kernel on the same inputs."""
+    probabilities within the path's 1e-4, every decision equal; (b) a full 4096-site chunk (one round of 32-site tiles on 256 CUs)
+    and ragged batches (1, 15, 16, 17, 33, 1000: whole and partial 16-site tiles) against the fp32 kernel on the same inputs.  All
+    of these are ONE launch range starting at site 0 (csrc/gru_tiles.h); a second range, ragged 32-site tiles and batches above one
+    round are in tests/test_gpu_bigru_layers.py."""
     import torch
     import oracle
     from clairs_to_amd.featurize import featurize
