@@ -90,6 +90,23 @@ class AfStats(C.Structure):
                 ("host_loci", c_i64), ("ms_inflate", C.c_double), ("ms_records", C.c_double), ("ms_count", C.c_double)]
 
 
+class HapRec(C.Structure):
+    _fields_ = [("read", c_i32), ("indel_off", c_i32), ("indel_len", c_i32), ("joined", c_i32), ("bq", c_i32), ("mq", c_i32),
+                ("base", C.c_uint8), ("hp", C.c_uint8), ("hp_single", C.c_uint8), ("pad_", C.c_uint8)]
+
+
+class HapView(C.Structure):
+    _fields_ = [("n_cols", c_i64), ("n_recs", c_i64), ("n_reads", c_i64), ("n_rse", c_i64), ("indel_bytes", c_i64), ("lo", c_i64), ("hi", c_i64),
+                ("col_pos", c_vp), ("col_off", c_vp), ("rse_off", c_vp), ("recs", c_vp), ("rse", c_vp), ("indels", c_vp)]
+
+
+class HapStats(C.Structure):
+    _fields_ = [("n_chunks", c_i64), ("n_reads_entered", c_i64), ("n_blocks", c_i64), ("inflated_bytes", c_i64), ("fallback_chunks", c_i64),
+                ("cap_chunks", c_i64), ("host_columns", c_i64), ("n_cols", c_i64), ("n_recs", c_i64), ("ms_read", C.c_double),
+                ("ms_inflate", C.c_double), ("ms_records", C.c_double), ("ms_kernels", C.c_double), ("ms_down", C.c_double),
+                ("ms_build", C.c_double)]
+
+
 class GermlineStats(C.Structure):
     _fields_ = [("n_runs", c_i64), ("n_probes", c_i64), ("host_path", c_i64), ("kernel_ms", C.c_double)]
 
@@ -184,6 +201,13 @@ SYMBOLS = {
     "cto_run_release": (C.c_int, []),
     "cto_haplotype_filter": (C.c_int, [c_vp, C.c_size_t, C.c_char_p, c_i64, C.c_size_t, c_i64, c_vp, c_vp, c_vp, c_vp, C.c_int, C.c_int,
                                        C.c_int, c_vp, c_vp]),
+    "cto_hap_job_from_text": (C.c_int, [c_vp, C.c_size_t, c_i64, c_i64, C.POINTER(c_vp)]),
+    "cto_hap_evaluate": (C.c_int, [c_vp, C.c_char_p, c_i64, C.c_size_t, c_i64, c_vp, c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_int, c_vp, c_vp]),
+    "cto_hap_job_free": (None, [c_vp]),
+    "cto_hap_job_view": (C.c_int, [c_vp, C.POINTER(HapView)]),
+    "cto_hap_job_key_string": (C.c_int, [c_vp, c_i64, C.POINTER(C.c_char_p)]),
+    "cto_hap_windows": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, c_i64, c_i64, c_vp, c_i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                  C.c_int, C.POINTER(c_vp), C.POINTER(HapStats)]),
     "cto_realign_reads": (C.c_int, [C.c_int, c_vp, c_vp, c_vp, C.c_char_p, C.c_char_p, c_i32, c_i32, c_i32, c_vp, c_vp, C.c_size_t, c_vp]),
     "cto_dev_tokeniser_create": (C.c_int, [C.POINTER(c_vp)]),
     "cto_dev_tokeniser_destroy": (None, [c_vp]),

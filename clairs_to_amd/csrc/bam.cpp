@@ -44,6 +44,7 @@
 #include <unordered_map>
 
 #include "bam_host.h"
+#include "hap_internal.h"
 #include "pack_internal.h"
 
 using namespace cto;
@@ -703,6 +704,150 @@ int af_tallies_host_range(const char* bam_path, const char* bai_path, const char
     if (n_entered) *n_entered = entered;
     if (ms_records) *ms_records = now() - t0 - t_count;
     if (ms_count) *ms_count = t_count;
+    return CTO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ haplotype windows, host path
+// The plain definition of the rules by which a haplotype-filter job is built from the BAM (listed in full at the top of
+// csrc/hapwindows.hip, which holds the C entry point and the device path that is held equal to this one): one pass in file order over
+// the reads that overlap the region, each walked along the wanted positions it covers.  Per column two lists grow side by side, as the
+// text has them: the COVERS (name, HP, BQ, MQ: one per read over the position that passes --min-BQ, reference skips included) and
+// the ENTRIES (base and indel: one per cover that is no skip).  Record i of a column is entry i with cover i's name, HP, BQ and MQ.
+int hap_windows_host(const char* bam_path, const char* bai_path, const char* ctg_name, int64_t region_lo, int64_t region_hi, const int64_t* iv,
+                     int64_t n_iv, const HapWinParams& pr, HapRaw* raw, int64_t* n_entered) {
+    if (n_entered) *n_entered = 0;
+    if (n_iv <= 0) return CTO_OK;
+    constexpr int32_t NONE = INT32_MIN;
+    struct Slot {                                       // cover i and entry i of a column share slot i
+        int32_t read; uint8_t bq, mq, base; int32_t indel_off, indel_len, start_idx, end_idx;
+    };
+    struct ColBuild { std::vector<Slot> s; int32_t n_cov = 0, n_ent = 0; };
+    std::vector<int64_t> base(size_t(n_iv) + 1, 0);
+    for (int64_t k = 0; k < n_iv; ++k) base[size_t(k) + 1] = base[size_t(k)] + (iv[2 * k + 1] - iv[2 * k]);
+    std::vector<ColBuild> cols(static_cast<size_t>(base[size_t(n_iv)]));
+    // the depth cap looks at every read of the region in front of the one it judges, so with a cap the pass starts at the region's start
+    const int64_t beg0 = pr.max_depth > 0 ? region_lo - 1 : std::max<int64_t>(region_lo - 1, iv[0]);
+    const int64_t end0 = std::min<int64_t>(region_hi, iv[2 * n_iv - 1]);
+    if (end0 <= beg0) return CTO_OK;
+    BamRegion rg;
+    CTO_REQUIRE(rg.open("cto_hap_windows", bam_path, bai_path, ctg_name, beg0, end0, false, false), CTO_EINVAL, "%s", rg.err.c_str());
+    std::vector<int32_t> live;                          // ends of the accepted reads still open (kept only under a cap)
+    int64_t entered = 0;
+    for (BamRecord b;;) {
+        const int got = rg.next(&b);
+        CTO_REQUIRE(got >= 0, CTO_EINVAL, "%s", rg.err.c_str());
+        if (got == 0) break;
+        const int flag = b.flag;
+        if ((flag & pr.excl_flags) || (flag & 4) || b.mapq < pr.min_mq || b.n_cig == 0 || b.l_seq <= 0 || b.pos < 0) continue;
+        if ((flag & 1) && !(flag & 2)) continue;           // orphan (mpileup without -A)
+        CTO_REQUIRE(rg.lay_out(&b), CTO_EINVAL, "%s", rg.err.c_str());
+        const int enters = rg.enters(b);
+        CTO_REQUIRE(enters >= 0, CTO_EINVAL, "%s", rg.err.c_str());
+        if (!enters) continue;
+        const int32_t rend = int32_t(b.pos + b.rlen);
+        if (pr.max_depth > 0) {
+            live.erase(std::remove_if(live.begin(), live.end(), [&](int32_t e) { return e <= b.pos; }), live.end());
+            if (int64_t(live.size()) >= pr.max_depth) continue;
+            live.push_back(rend);
+        }
+        ++entered;
+        // first wanted interval that ends behind the read's start
+        int64_t kiv = 0;
+        for (int64_t z = n_iv; kiv < z;) { const int64_t m = (kiv + z) >> 1; if (iv[2 * m + 1] > b.pos) z = m; else kiv = m + 1; }
+        if (kiv >= n_iv || iv[2 * kiv] >= rend) continue;
+        const bool rev = (flag & 16) != 0, no_qual = b.ql[0] == 0xff;
+        const uint8_t mq = uint8_t(std::min(b.mapq, 93));
+        auto base4 = [&](int q) { return (b.sq[q >> 1] >> ((~q & 1) << 2)) & 15; };
+        auto bq_at = [&](int q) { return (no_qual || q >= b.l_seq) ? 0 : std::min(int(b.ql[q]), 93); };
+        int32_t ridx = -1;
+        int32_t rp = b.pos, qp = 0;
+        for (int k = 0; k < b.n_ops && kiv < n_iv; ++k) {
+            const int len = int(b.op(k) >> 4), opc = int(b.op(k) & 15);
+            const bool cons_ref = consumes_ref(opc), cons_q = consumes_query(opc);
+            if (cons_ref) {
+                const int64_t op_end = int64_t(rp) + len;
+                while (kiv < n_iv && iv[2 * kiv] < op_end) {
+                    const int64_t s = iv[2 * kiv], e = iv[2 * kiv + 1];
+                    for (int64_t p = std::max<int64_t>(rp, s); p < std::min(op_end, e); ++p) {
+                        const bool placeholder = opc == 2 || opc == 3;
+                        const int q = placeholder ? qp : qp + int(p - rp);      // a deletion or skip: the query base that follows it
+                        const int bqv = bq_at(q);
+                        if (bqv < pr.min_bq) continue;     // prints nothing: base, ^ and $, quality, name and HP go together
+                        if (ridx < 0) {
+                            ridx = int32_t(raw->names.size());
+                            raw->names.emplace_back(reinterpret_cast<const char*>(b.name), size_t(std::max(0, b.l_name - 1)));
+                            int hp = 0;
+                            const uint8_t* aux = b.aux;
+                            long long val;
+                            for (AuxField f; aux_next(&aux, b.end, &f);)
+                                if (f.t0 == 'H' && f.t1 == 'P' && aux_int(f, &val)) { hp = val == 1 ? 1 : (val == 2 ? 2 : (val == 12 ? 3 : 0)); break; }
+                            raw->hp.push_back(uint8_t(hp));
+                        }
+                        ColBuild& c = cols[size_t(base[size_t(kiv)] + (p - s))];
+                        const int32_t ci = c.n_cov++;
+                        if (size_t(ci) == c.s.size()) c.s.push_back(Slot{});
+                        c.s[size_t(ci)].read = ridx;
+                        c.s[size_t(ci)].bq = uint8_t(bqv);
+                        c.s[size_t(ci)].mq = mq;
+                        c.s[size_t(ci)].start_idx = p == b.pos ? c.n_ent - 1 : NONE;       // ^ stands in front of the base: the record before it
+                        if (opc != 3) {
+                            Slot& en = c.s[size_t(c.n_ent++)];
+                            en.indel_off = en.indel_len = 0;
+                            if (opc == 2) en.base = uint8_t(rev && pr.reverse_del ? '#' : '*');
+                            else {
+                                const int c4 = base4(q);
+                                const char letter = c4 == 1 ? 'A' : (c4 == 2 ? 'C' : (c4 == 4 ? 'G' : (c4 == 8 ? 'T' : 'N')));
+                                en.base = uint8_t(rev ? letter + 32 : letter);
+                                if (p == op_end - 1) {         // the operation's last base: does an indel follow?
+                                    int nx = k + 1;
+                                    while (nx < b.n_ops && (b.op(nx) & 15) == 6) ++nx;      // P
+                                    const int nop = nx < b.n_ops ? int(b.op(nx) & 15) : -1, nlen = nx < b.n_ops ? int(b.op(nx) >> 4) : 0;
+                                    if (nop == 1 || nop == 2) {
+                                        en.indel_off = int32_t(raw->indel.size());
+                                        en.indel_len = nlen + 1;
+                                        raw->indel.push_back(nop == 1 ? '+' : '-');
+                                        for (int x = 0; x < nlen; ++x) {
+                                            char ib = 'N';
+                                            if (nop == 1) { ib = kNt16[base4(q + 1 + x)]; if (ib == '=') ib = 'N'; }
+                                            raw->indel.push_back(rev ? char(ib + 32) : ib);
+                                        }
+                                    }
+                                }
+                            }
+                        }
+                        c.s[size_t(ci)].end_idx = p == rend - 1 ? c.n_ent - 1 : NONE;       // $ stands behind it
+                    }
+                    if (e <= op_end) ++kiv; else break;
+                }
+                rp += len;
+            }
+            if (cons_q) qp += len;
+        }
+    }
+    // the columns that hold a record (one with covers but no entry is left out: see csrc/hapwindows.hip)
+    std::vector<int32_t> starts, ends;
+    for (int64_t k = 0; k < n_iv; ++k)
+        for (int64_t p = iv[2 * k]; p < iv[2 * k + 1]; ++p) {
+            const ColBuild& c = cols[size_t(base[size_t(k)] + (p - iv[2 * k]))];
+            if (c.n_ent == 0) continue;
+            starts.clear();
+            ends.clear();
+            for (int32_t i = 0; i < c.n_cov; ++i) {
+                const Slot& s = c.s[size_t(i)];
+                if (s.start_idx != NONE) starts.push_back(s.start_idx);
+                if (s.end_idx != NONE) ends.push_back(s.end_idx);
+                if (i < c.n_ent) raw->recs.push_back(HapRawRec{s.read, s.base, s.bq, s.mq, 0, s.indel_off, s.indel_len});
+            }
+            auto uniq = [](std::vector<int32_t>& v) { std::sort(v.begin(), v.end()); v.erase(std::unique(v.begin(), v.end()), v.end()); };
+            uniq(starts);
+            uniq(ends);
+            const std::vector<int32_t>& win = starts.size() > ends.size() ? starts : ends;
+            raw->rse.insert(raw->rse.end(), win.begin(), win.end());
+            raw->col_pos.push_back(p + 1);
+            raw->col_off.push_back(int64_t(raw->recs.size()));
+            raw->rse_off.push_back(int64_t(raw->rse.size()));
+        }
+    if (n_entered) *n_entered = entered;
     return CTO_OK;
 }
 

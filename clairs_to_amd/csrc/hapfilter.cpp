@@ -13,38 +13,56 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <unordered_map>
 #include <vector>
 #include "common.h"
+#include "hap_internal.h"
 
 using namespace cto;
 
 namespace {
 
-struct Rec {
-    int read;            // interned "<qname>_<0|1>" (strand suffix from the base's case, :251-255)
-    char base;           // upper-cased base character: A C G T N * #
-    int indel_off, indel_len;   // sign + sequence as printed (raw case), empty when none
-    int joined;          // id of upper(base + indel), the key of the column's Counter (:186)
-    int bq, mq;
-    char hp;             // first character of the HP field ('1', '2', anything else = untagged)
-    bool hp_single;      // the HP field is exactly one character
+inline char up(char c) { return (c >= 'a' && c <= 'z') ? char(c - 32) : c; }
+
+using Rec = cto_hap_rec;          // read: interned "<qname>_<0|1>" (strand suffix from the base's case, :251-255); base: upper-cased
+                                  // A C G T N * #; indel_off / indel_len: sign + sequence as printed (raw case), empty when none;
+                                  // joined: id of upper(base + indel), the key of the column's Counter (:186); hp: first character of
+                                  // the HP field ('1', '2', anything else = untagged); hp_single: the field is exactly one character
+
+template <class T>
+struct Span {
+    const T *b = nullptr, *e = nullptr;
+    const T* begin() const { return b; }
+    const T* end() const { return e; }
+    size_t size() const { return size_t(e - b); }
+    bool empty() const { return b == e; }
+    const T& operator[](size_t i) const { return b[i]; }
 };
 
-struct Column {
+struct Column {                    // a view of one column of the job
     int64_t pos = 0;
+    Span<Rec> recs;
+    Span<int> rse;                 // record indices flagged as read start / end (:176-185), -1 = "the last record" (Python index)
+};
+
+struct TextColumn {                // a column while the text is parsed (a repeated position replaces the earlier row)
     std::vector<Rec> recs;
-    std::vector<int> rse;          // record indices flagged as read start / end (:176-185), -1 = "the last record" (Python index)
+    std::vector<int> rse;
     bool present = false;
 };
 
+// The job: columns in ascending position, CSR - the records of column c are recs[col_off[c] .. col_off[c + 1]), its start / end
+// indices rse[rse_off[c] .. rse_off[c + 1]).  These arrays are what cto_hap_job_view shows and what every producer fills.
 struct Job {
     std::string text_indels;       // backing store for indel strings
-    std::vector<Column> cols;      // dense over [lo, hi]
+    std::vector<int64_t> col_pos, col_off{0}, rse_off{0};
+    std::vector<Rec> recs;
+    std::vector<int32_t> rse;
     int64_t lo = 0, hi = -1;
     std::unordered_map<std::string, int> read_ids, joined_ids;
-    std::vector<std::string> joined_names;
+    std::vector<std::string> joined_names, read_keys;
     std::vector<char> read_rev;    // per read id: the "_1" (reverse strand) suffix
     int intern(std::unordered_map<std::string, int>& m, const std::string& s, std::vector<std::string>* names = nullptr) {
         auto it = m.find(s);
@@ -54,17 +72,35 @@ struct Job {
         if (names) names->push_back(s);
         return id;
     }
-    const Column* at(int64_t p) const {
-        if (p < lo || p > hi) return nullptr;
-        const Column& c = cols[size_t(p - lo)];
-        return c.present ? &c : nullptr;
+    int intern_read(const std::string& key, bool rev) {
+        const int id = intern(read_ids, key, &read_keys);
+        if (size_t(id) == read_rev.size()) read_rev.push_back(rev ? 1 : 0);
+        return id;
+    }
+    int intern_joined(const Rec& r, std::string& key) {
+        key.assign(1, char(r.base));
+        for (int k = 0; k < r.indel_len; ++k) key.push_back(up(text_indels[size_t(r.indel_off + k)]));
+        return intern(joined_ids, key, &joined_names);
+    }
+    void end_column(int64_t pos) {                      // the records and indices appended since the last call are column `pos`
+        col_pos.push_back(pos);
+        col_off.push_back(int64_t(recs.size()));
+        rse_off.push_back(int64_t(rse.size()));
+    }
+    bool at(int64_t p, Column* c) const {
+        if (p < lo || p > hi) return false;
+        const auto it = std::lower_bound(col_pos.begin(), col_pos.end(), p);
+        if (it == col_pos.end() || *it != p) return false;
+        const size_t k = size_t(it - col_pos.begin());
+        c->pos = p;
+        c->recs = Span<Rec>{recs.data() + col_off[k], recs.data() + col_off[k + 1]};
+        c->rse = Span<int>{rse.data() + rse_off[k], rse.data() + rse_off[k + 1]};
+        return true;
     }
 };
 
-inline char up(char c) { return (c >= 'a' && c <= 'z') ? char(c - 32) : c; }
-
 // haplotype_filtering.py:157-187 (get_base_list) + :244-272 (_parse_mpileup_to_chunk_dict) for one row
-int parse_row(const char* row, const char* end, Job& job, int64_t lo, int64_t hi) {
+int parse_row(const char* row, const char* end, Job& job, std::vector<TextColumn>& cols, int64_t lo, int64_t hi) {
     const char* f[10];
     int nf = 0;
     f[nf++] = row;
@@ -78,10 +114,9 @@ int parse_row(const char* row, const char* end, Job& job, int64_t lo, int64_t hi
         pos = pos * 10 + (*q - '0');
     }
     if (pos < lo || pos > hi) return CTO_OK;
-    Column& col = job.cols[size_t(pos - lo)];
+    TextColumn& col = cols[size_t(pos - lo)];
     col.recs.clear();                                   // a repeated position replaces the earlier row (dict assignment)
     col.rse.clear();
-    col.pos = pos;
     col.present = true;
     std::vector<int> starts, ends;
     const char* bs = f[4];
@@ -144,18 +179,15 @@ int parse_row(const char* row, const char* end, Job& job, int64_t lo, int64_t hi
         const bool rev = r.base == '#' || (r.base >= 'a' && r.base <= 'z');
         key.assign(nm, size_t(ne - nm));
         key += rev ? "_1" : "_0";
-        r.read = job.intern(job.read_ids, key);
-        if (size_t(r.read) == job.read_rev.size()) job.read_rev.push_back(rev ? 1 : 0);
+        r.read = job.intern_read(key, rev);
         nm = ne + 1;
         const char* he = static_cast<const char*>(memchr(hp, ',', size_t(hpe > hp ? hpe - hp : 0)));
         if (!he) he = hpe;
         r.hp = (he > hp) ? hp[0] : '\0';
         r.hp_single = (he - hp) == 1;
         hp = he + 1;
-        r.base = up(r.base);
-        key.assign(1, r.base);
-        for (int k = 0; k < r.indel_len; ++k) key.push_back(up(job.text_indels[size_t(r.indel_off + k)]));
-        r.joined = job.intern(job.joined_ids, key, &job.joined_names);
+        r.base = uint8_t(up(char(r.base)));
+        r.joined = job.intern_joined(r, key);
     }
     return CTO_OK;
 }
@@ -242,30 +274,154 @@ enum { F_PHASEABLE = 0, F_HETERO, F_HOMO, F_RSE, F_BQ, F_MQ, F_COEXIST, F_BOTH_S
 //                       hetero-both-side, sequence entropy)
 //   strand[n][4]        a0, r0, a1, r1 of the 2x2 table for Fisher's exact test (:575-582; the caller computes the p-value in
 //                       exact integer arithmetic as the reference does) - int64
-extern "C" int cto_haplotype_filter(const char* text, size_t len, const char* ref_seq, int64_t region_lo, size_t ref_len, int64_t n,
-                                    const int32_t* pos, const char* fields, const int64_t* field_off, const double* af, int flanking,
-                                    int max_co_exist_read_num, int disable_rse, uint8_t* flags, int64_t* strand) try {
-    CTO_REQUIRE(text && ref_seq && (n == 0 || (pos && fields && field_off && af && flags && strand)) && flanking > 0, CTO_EINVAL,
-                "cto_haplotype_filter: bad argument");
-    if (n == 0) return CTO_OK;
-    Job job;
-    job.lo = std::max<int64_t>(1, int64_t(*std::min_element(pos, pos + n)) - flanking);
-    job.hi = int64_t(*std::max_element(pos, pos + n)) + flanking;
-    CTO_REQUIRE(job.hi - job.lo < (int64_t(1) << 26), CTO_EUNSUPPORTED, "cto_haplotype_filter: job spans more than 64 Mb; split it");
-    job.cols.resize(size_t(job.hi - job.lo + 1));
+//
+// The work is two halves with the job object between them.  A PRODUCER builds the job: cto_hap_job_from_text from the nine-column
+// text (the rows whose position lies in [lo, hi]), cto_hap_windows (csrc/hapwindows.hip) from the BAM itself.  cto_hap_evaluate
+// applies the per-call rules to it.  cto_haplotype_filter is the text producer, the evaluation and the release in a row.
+extern "C" int cto_hap_job_from_text(const char* text, size_t len, int64_t lo, int64_t hi, void** out) try {
+    CTO_REQUIRE(text && out && lo >= 1 && hi >= lo, CTO_EINVAL, "cto_hap_job_from_text: bad argument");
+    CTO_REQUIRE(hi - lo < (int64_t(1) << 26), CTO_EUNSUPPORTED, "cto_hap_job_from_text: job spans more than 64 Mb; split it");
+    *out = nullptr;
+    std::unique_ptr<Job> jp(new Job);
+    Job& job = *jp;
+    job.lo = lo;
+    job.hi = hi;
+    std::vector<TextColumn> cols(size_t(hi - lo + 1));
     for (const char* cur = text; cur < text + len;) {
         const char* eol = static_cast<const char*>(memchr(cur, '\n', size_t(text + len - cur)));
         if (!eol) eol = text + len;
         if (eol > cur) {
-            const int rc = parse_row(cur, eol, job, job.lo, job.hi);
+            const int rc = parse_row(cur, eol, job, cols, lo, hi);
             if (rc != CTO_OK) return rc;
         }
         cur = eol + 1;
     }
+    for (size_t i = 0; i < cols.size(); ++i) {
+        TextColumn& c = cols[i];
+        if (!c.present) continue;
+        job.recs.insert(job.recs.end(), c.recs.begin(), c.recs.end());
+        job.rse.insert(job.rse.end(), c.rse.begin(), c.rse.end());
+        job.end_column(lo + int64_t(i));
+        std::vector<Rec>().swap(c.recs);
+    }
+    *out = jp.release();
+    return CTO_OK;
+} CTO_CATCH("cto_hap_job_from_text", int)
+
+extern "C" void cto_hap_job_free(void* job) { delete static_cast<Job*>(job); }
+
+extern "C" int cto_hap_job_view(const void* job, cto_hap_view* v) try {
+    CTO_REQUIRE(job && v, CTO_EINVAL, "cto_hap_job_view: null argument");
+    const Job& j = *static_cast<const Job*>(job);
+    v->n_cols = int64_t(j.col_pos.size());
+    v->n_recs = int64_t(j.recs.size());
+    v->n_reads = int64_t(j.read_keys.size());
+    v->n_rse = int64_t(j.rse.size());
+    v->indel_bytes = int64_t(j.text_indels.size());
+    v->lo = j.lo;
+    v->hi = j.hi;
+    v->col_pos = j.col_pos.data();
+    v->col_off = j.col_off.data();
+    v->rse_off = j.rse_off.data();
+    v->recs = j.recs.data();
+    v->rse = j.rse.data();
+    v->indels = j.text_indels.data();
+    return CTO_OK;
+} CTO_CATCH("cto_hap_job_view", int)
+
+extern "C" int cto_hap_job_key_string(const void* job, int64_t read, const char** s) try {
+    CTO_REQUIRE(job && s, CTO_EINVAL, "cto_hap_job_key_string: null argument");
+    const Job& j = *static_cast<const Job*>(job);
+    CTO_REQUIRE(read >= 0 && read < int64_t(j.read_keys.size()), CTO_EINVAL, "cto_hap_job_key_string: no read %lld in the job", (long long)read);
+    *s = j.read_keys[size_t(read)].c_str();
+    return CTO_OK;
+} CTO_CATCH("cto_hap_job_key_string", int)
+
+// the builder the BAM producers use (hap_internal.h)
+namespace cto {
+
+int hap_job_new(int64_t lo, int64_t hi, void** out) try {
+    CTO_REQUIRE(out && lo >= 1 && hi >= lo, CTO_EINVAL, "cto_hap_windows: bad region");
+    CTO_REQUIRE(hi - lo < (int64_t(1) << 26), CTO_EUNSUPPORTED, "cto_hap_windows: job spans more than 64 Mb; split it");
+    Job* j = new Job;
+    j->lo = lo;
+    j->hi = hi;
+    *out = j;
+    return CTO_OK;
+} CTO_CATCH("cto_hap_windows", int)
+
+int hap_job_add(void* jobp, const HapRaw& raw, int64_t c0, int64_t c1) try {
+    Job& job = *static_cast<Job*>(jobp);
+    std::vector<int> ids(raw.names.size() * 2, -1);     // [read][strand suffix] -> interned id: a name is hashed once per strand
+    std::string key;
+    for (int64_t c = c0; c < c1; ++c) {
+        CTO_REQUIRE(job.col_pos.empty() || raw.col_pos[size_t(c)] > job.col_pos.back(), CTO_EINVAL, "cto_hap_windows: columns out of order");
+        for (int64_t i = raw.col_off[size_t(c)]; i < raw.col_off[size_t(c) + 1]; ++i) {
+            const HapRawRec& s = raw.recs[size_t(i)];
+            const bool rev = s.base == '#' || (s.base >= 'a' && s.base <= 'z');
+            int& id = ids[size_t(s.read) * 2 + (rev ? 1 : 0)];
+            if (id < 0) {
+                key = raw.names[size_t(s.read)];
+                key += rev ? "_1" : "_0";
+                id = job.intern_read(key, rev);
+            }
+            const int h = raw.hp[size_t(s.read)];
+            Rec r{};
+            r.read = id;
+            r.base = uint8_t(up(char(s.base)));
+            if (s.indel_len) {
+                CTO_REQUIRE(job.text_indels.size() + size_t(s.indel_len) < (size_t(1) << 31), CTO_EUNSUPPORTED,
+                            "cto_hap_windows: more than 2 GiB of indel sequence in one job");
+                r.indel_off = int32_t(job.text_indels.size());
+                r.indel_len = s.indel_len;
+                job.text_indels.append(raw.indel, size_t(s.indel_off), size_t(s.indel_len));
+            }
+            r.bq = s.bq;
+            r.mq = s.mq;
+            r.hp = uint8_t(h == 1 || h == 3 ? '1' : (h == 2 ? '2' : '*'));          // 3: "12" - two characters, untagged
+            r.hp_single = h != 3;
+            r.joined = job.intern_joined(r, key);
+            job.recs.push_back(r);
+        }
+        job.rse.insert(job.rse.end(), raw.rse.begin() + raw.rse_off[size_t(c)], raw.rse.begin() + raw.rse_off[size_t(c) + 1]);
+        job.end_column(raw.col_pos[size_t(c)]);
+    }
+    return CTO_OK;
+} CTO_CATCH("cto_hap_windows", int)
+
+}  // namespace cto
+
+extern "C" int cto_haplotype_filter(const char* text, size_t len, const char* ref_seq, int64_t region_lo, size_t ref_len, int64_t n,
+                                    const int32_t* pos, const char* fields, const int64_t* field_off, const double* af, int flanking,
+                                    int max_co_exist_read_num, int disable_rse, uint8_t* flags, int64_t* strand) {
+    if (!(text && ref_seq && (n == 0 || (pos && fields && field_off && af && flags && strand)) && flanking > 0)) {
+        set_error("cto_haplotype_filter: bad argument");
+        return CTO_EINVAL;
+    }
+    if (n == 0) return CTO_OK;
+    const int64_t lo = std::max<int64_t>(1, int64_t(*std::min_element(pos, pos + n)) - flanking);
+    const int64_t hi = int64_t(*std::max_element(pos, pos + n)) + flanking;
+    void* job = nullptr;
+    int rc = cto_hap_job_from_text(text, len, lo, hi, &job);
+    if (rc == CTO_OK)
+        rc = cto_hap_evaluate(job, ref_seq, region_lo, ref_len, n, pos, fields, field_off, af, flanking, max_co_exist_read_num, disable_rse, flags, strand);
+    cto_hap_job_free(job);
+    return rc;
+}
+
+extern "C" int cto_hap_evaluate(const void* jobp, const char* ref_seq, int64_t region_lo, size_t ref_len, int64_t n, const int32_t* pos,
+                                const char* fields, const int64_t* field_off, const double* af, int flanking, int max_co_exist_read_num,
+                                int disable_rse, uint8_t* flags, int64_t* strand) try {
+    CTO_REQUIRE(jobp && ref_seq && (n == 0 || (pos && fields && field_off && af && flags && strand)) && flanking > 0, CTO_EINVAL,
+                "cto_hap_evaluate: bad argument");
+    if (n == 0) return CTO_OK;
+    const Job& job = *static_cast<const Job*>(jobp);
     const int n_reads = int(job.read_ids.size());
     std::vector<int> hap(size_t(n_reads) + 1);           // hap_dict: 0 unless assigned (:608-612)
     std::vector<char> is_alt(size_t(n_reads) + 1), in_rse(size_t(n_reads) + 1), mark(size_t(n_reads) + 1);
     std::vector<GermSite> hetero, homo;
+    Column col_view;                                    // one column is looked at at a time
+    auto col_at = [&](int64_t p) -> const Column* { return job.at(p, &col_view) ? &col_view : nullptr; };
     std::vector<int> alt_reads, tmp_ids, cnt_ids, cnt_vals;
     for (int64_t v = 0; v < n; ++v) {
         uint8_t* fl = flags + v * F_NFLAGS;
@@ -328,7 +484,7 @@ extern "C" int cto_haplotype_filter(const char* text, size_t len, const char* re
         };
         // ---- pass over the window: haplotypes, start / end reads, evidence at the call itself (:603-707) ----
         for (int64_t p = win_lo; p <= win_hi; ++p) {
-            const Column* c = job.at(p);
+            const Column* c = col_at(p);
             if (!c) continue;
             if (p == p0 || is_het_pos(p)) {
                 // a read's haplotype is taken from the call position and from heterozygous germline positions only, first
@@ -385,7 +541,7 @@ extern "C" int cto_haplotype_filter(const char* text, size_t len, const char* re
         // ---- variant cluster (:390-441) ----
         int64_t match_count = 0, ins_length = 0;
         for (int64_t p = win_lo; p <= win_hi; ++p) {
-            const Column* c = job.at(p);
+            const Column* c = col_at(p);
             char rb;
             if (!c || !site_ref(p, &rb) || p == p0) continue;
             // last record of every read name at this position
@@ -462,7 +618,7 @@ extern "C" int cto_haplotype_filter(const char* text, size_t len, const char* re
         };
         if (hap_index > 0) {
             for (const GermSite& g : hetero) {
-                const Column* c = (g.pos >= win_lo && g.pos <= win_hi) ? job.at(g.pos) : nullptr;
+                const Column* c = (g.pos >= win_lo && g.pos <= win_hi) ? col_at(g.pos) : nullptr;
                 char rb;
                 if (!c || !site_ref(g.pos, &rb) || g.alt.empty()) continue;
                 last_records(c);
@@ -482,7 +638,7 @@ extern "C" int cto_haplotype_filter(const char* text, size_t len, const char* re
         }
         // ---- ancestry on homozygous germline variants (:478-541) ----
         for (const GermSite& g : homo) {
-            const Column* c = (g.pos >= win_lo && g.pos <= win_hi) ? job.at(g.pos) : nullptr;
+            const Column* c = (g.pos >= win_lo && g.pos <= win_hi) ? col_at(g.pos) : nullptr;
             char rb;
             if (!c || !site_ref(g.pos, &rb) || g.alt.empty()) continue;
             last_records(c);
@@ -525,4 +681,4 @@ extern "C" int cto_haplotype_filter(const char* text, size_t len, const char* re
         }
     }
     return CTO_OK;
-} CTO_CATCH("cto_haplotype_filter", int)
+} CTO_CATCH("cto_hap_evaluate", int)

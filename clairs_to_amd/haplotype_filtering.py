@@ -8,7 +8,9 @@ Same inputs, options and output VCF as the reference.  What differs is how the w
 calls of a contig are cut into mpileup jobs, each job's nine-column `samtools mpileup --output-QNAME --output-extra HP` text is
 handed to ONE C call (cto_haplotype_filter, csrc/hapfilter.cpp) that evaluates every read-level rule for every call of the
 job, and Python keeps what is exact integer arithmetic in the reference (Fisher's test on the returned 2x2 table) and the VCF
-text.  There is no device work in this stage (thousands of calls, not millions of sites).
+text.  With `--pileup_source bam` no text exists: the job object is built from the BAM's alignment records (cto_hap_windows,
+csrc/hapwindows.hip: inflate, records and the pile-up of the calls' windows on the device, or `--where host`) and handed to
+cto_hap_evaluate - the same rules on the same records.
 """
 import bisect
 import ctypes as C
@@ -172,9 +174,7 @@ def mpileup_text(args, contig, lo, hi, positions, flanking):
     if getattr(args, "mpileup_fn", None):
         with open(args.mpileup_fn, "rb") as f:
             return f.read()
-    bam = args.tumor_bam_fn
-    if not os.path.isfile(bam) and not bam.endswith(".bam"):
-        bam = bam + contig + ".bam"                      # phased-prefix mode of run_clairs_to --phase_tumor (:275-280)
+    bam = resolve_bam(args, contig)
     fd, bed = tempfile.mkstemp(suffix=".bed", prefix="hf_mpileup_")
     try:
         with os.fdopen(fd, "w") as f:
@@ -195,8 +195,7 @@ def mpileup_text(args, contig, lo, hi, positions, flanking):
             pass
 
 
-def evaluate_job(text, ref_seq, region_lo, calls, flanking, max_co_exist_read_num, disable_rse):
-    """calls: [(pos, ref, alt, af, hetero_info, homo_info)] -> [dict(flags..., strand table)] through cto_haplotype_filter"""
+def _call_arrays(calls):
     n = len(calls)
     pos = np.array([c[0] for c in calls], dtype=np.int32)
     af = np.array([1.0 if c[3] is None else float(c[3]) for c in calls], dtype=np.float64)
@@ -206,15 +205,11 @@ def evaluate_job(text, ref_seq, region_lo, calls, flanking, max_co_exist_read_nu
         fields.append(b)
         off[i + 1] = off[i] + len(b)
     blob = b"".join(fields)
-    flags = np.zeros((n, len(FLAG_NAMES)), dtype=np.uint8)
-    strand = np.zeros((n, 4), dtype=np.int64)
-    tb = text if isinstance(text, (bytes, bytearray)) else text.encode()
-    rb = ref_seq.encode() if isinstance(ref_seq, str) else ref_seq
     fb = np.frombuffer(blob, dtype=np.uint8) if blob else np.zeros(1, dtype=np.uint8)
-    tarr = np.frombuffer(tb, dtype=np.uint8) if len(tb) else np.zeros(1, dtype=np.uint8)
-    check(lib.cto_haplotype_filter(tarr.ctypes.data, len(tb), rb, int(region_lo), len(rb), n, pos.ctypes.data, fb.ctypes.data,
-                                   off.ctypes.data, af.ctypes.data, int(flanking), int(max_co_exist_read_num), int(bool(disable_rse)),
-                                   flags.ctypes.data, strand.ctypes.data))
+    return pos, af, fb, off, np.zeros((n, len(FLAG_NAMES)), dtype=np.uint8), np.zeros((n, 4), dtype=np.int64)
+
+
+def _call_results(calls, flags, strand):
     out = []
     for i, c in enumerate(calls):
         a0, r0, a1, r1 = (int(v) for v in strand[i])
@@ -227,6 +222,104 @@ def evaluate_job(text, ref_seq, region_lo, calls, flanking, max_co_exist_read_nu
         d["pass_hap"] = all(d[k] for k in FLAG_NAMES[1:]) and d["strand_bias"]
         out.append(d)
     return out
+
+
+def evaluate_job(text, ref_seq, region_lo, calls, flanking, max_co_exist_read_num, disable_rse):
+    """calls: [(pos, ref, alt, af, hetero_info, homo_info)] -> [dict(flags..., strand table)] through cto_haplotype_filter"""
+    pos, af, fb, off, flags, strand = _call_arrays(calls)
+    tb = text if isinstance(text, (bytes, bytearray)) else text.encode()
+    rb = ref_seq.encode() if isinstance(ref_seq, str) else ref_seq
+    tarr = np.frombuffer(tb, dtype=np.uint8) if len(tb) else np.zeros(1, dtype=np.uint8)
+    check(lib.cto_haplotype_filter(tarr.ctypes.data, len(tb), rb, int(region_lo), len(rb), len(calls), pos.ctypes.data, fb.ctypes.data,
+                                   off.ctypes.data, af.ctypes.data, int(flanking), int(max_co_exist_read_num), int(bool(disable_rse)),
+                                   flags.ctypes.data, strand.ctypes.data))
+    return _call_results(calls, flags, strand)
+
+
+REC_DTYPE = np.dtype([("read", "<i4"), ("indel_off", "<i4"), ("indel_len", "<i4"), ("joined", "<i4"), ("bq", "<i4"), ("mq", "<i4"),
+                      ("base", "u1"), ("hp", "u1"), ("hp_single", "u1"), ("pad_", "u1")])
+EXCL_FLAGS, SAMTOOLS_MAX_DEPTH = 2316, 8000          # --excl-flags of the reference's command (:341); samtools mpileup's default -d
+
+
+class HapJob(object):
+    """One job object of csrc/hapfilter.cpp: built by a producer (from_text: the nine-column text; from_bam: cto_hap_windows, the
+    BAM itself, no text anywhere), evaluated by cto_hap_evaluate, released by close()."""
+
+    def __init__(self, handle, stats=None):
+        self.handle, self.stats = handle, stats
+
+    @classmethod
+    def from_text(cls, text, lo, hi):
+        tb = text if isinstance(text, (bytes, bytearray)) else text.encode()
+        tarr = np.frombuffer(tb, dtype=np.uint8) if len(tb) else np.zeros(1, dtype=np.uint8)
+        h = C.c_void_p()
+        check(lib.cto_hap_job_from_text(tarr.ctypes.data, len(tb), int(lo), int(hi), C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_bam(cls, bam, ctg, lo, hi, intervals=None, min_mq=20, min_bq=0, excl_flags=EXCL_FLAGS, max_depth=SAMTOOLS_MAX_DEPTH,
+                 reverse_del=False, where="device", bai=None):
+        """-r ctg:lo-hi (1-based, inclusive); intervals: merged 0-based [s, e) pairs (-l), None = the whole span"""
+        from ._lib import HapStats
+        if where not in ("device", "host"):
+            raise ValueError("where must be 'device' or 'host'")
+        if intervals is not None:
+            iv = np.ascontiguousarray(np.asarray(intervals, dtype=np.int64).reshape(-1, 2))
+        h, st = C.c_void_p(), HapStats()
+        check(lib.cto_hap_windows(str(bam).encode(), str(bai).encode() if bai else None, ctg.encode(), int(lo), int(hi),
+                                  iv.ctypes.data if intervals is not None else None, len(iv) if intervals is not None else 0, int(min_mq),
+                                  int(min_bq), int(excl_flags), int(max_depth), int(bool(reverse_del)), 1 if where == "device" else 0,
+                                  C.byref(h), C.byref(st)))
+        return cls(h, {k: getattr(st, k) for k, _ in HapStats._fields_})
+
+    def evaluate(self, ref_seq, region_lo, calls, flanking, max_co_exist_read_num, disable_rse):
+        pos, af, fb, off, flags, strand = _call_arrays(calls)
+        rb = ref_seq.encode() if isinstance(ref_seq, str) else ref_seq
+        check(lib.cto_hap_evaluate(self.handle, rb, int(region_lo), len(rb), len(calls), pos.ctypes.data, fb.ctypes.data, off.ctypes.data,
+                                   af.ctypes.data, int(flanking), int(max_co_exist_read_num), int(bool(disable_rse)), flags.ctypes.data,
+                                   strand.ctypes.data))
+        return _call_results(calls, flags, strand)
+
+    def view(self):
+        """copies of the job's arrays (cto_hap_job_view): dict(lo, hi, col_pos, col_off, rse_off, recs (REC_DTYPE), rse, indels
+        (bytes), keys ["<qname>_<0|1>" per read id])"""
+        from ._lib import HapView
+        v = HapView()
+        check(lib.cto_hap_job_view(self.handle, C.byref(v)))
+
+        def arr(ptr, n, dt):
+            return np.frombuffer(C.string_at(ptr, n * np.dtype(dt).itemsize), dtype=dt).copy() if n else np.zeros(0, dtype=dt)
+        keys = []
+        for k in range(v.n_reads):
+            s = C.c_char_p()
+            check(lib.cto_hap_job_key_string(self.handle, k, C.byref(s)))
+            keys.append(s.value.decode())
+        return dict(lo=v.lo, hi=v.hi, col_pos=arr(v.col_pos, v.n_cols, "<i8"), col_off=arr(v.col_off, v.n_cols + 1, "<i8"),
+                    rse_off=arr(v.rse_off, v.n_cols + 1, "<i8"), recs=arr(v.recs, v.n_recs, REC_DTYPE), rse=arr(v.rse, v.n_rse, "<i4"),
+                    indels=C.string_at(v.indels, v.indel_bytes) if v.indel_bytes else b"", keys=keys)
+
+    def close(self):
+        if self.handle:
+            lib.cto_hap_job_free(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def resolve_bam(args, contig):
+    bam = args.tumor_bam_fn
+    if not os.path.isfile(bam) and not bam.endswith(".bam"):
+        bam = bam + contig + ".bam"                      # phased-prefix mode of run_clairs_to --phase_tumor (:275-280)
+    return bam
+
+
+def _default_where():
+    import torch
+    return "device" if torch.cuda.is_available() else "host"
 
 
 # ------------------------------------------------------------------------------------------ the stage
@@ -279,10 +372,18 @@ def haplotype_filter(args):
     results = {}
     jobs = partition_jobs(calls.keys(), flanking, args.haplotype_chunk_max_sites, args.haplotype_chunk_max_span)
 
+    from_bam = getattr(args, "pileup_source", "samtools") == "bam" and not getattr(args, "mpileup_fn", None)
+    where = (getattr(args, "where", None) or _default_where()) if from_bam else None
+
     def run_job(job):
         lo, hi, ps = job
-        text = mpileup_text(args, ctg_name, lo, hi, ps, flanking)
         ref = read_region(args.ref_fn, ctg_name, lo, hi)
+        if from_bam:                                     # the job straight from the BAM (cto_hap_windows): no text anywhere
+            iv = flank_bed(ps, flanking) if getattr(args, "haplotype_chunk_mpileup_bed", True) else None
+            with HapJob.from_bam(resolve_bam(args, ctg_name), ctg_name, lo, hi, iv, min_mq=args.min_mq, min_bq=args.min_bq,
+                                 reverse_del=getattr(args, "reverse_del", False), where=where, bai=getattr(args, "bai_fn", None)) as hj:
+                return hj.evaluate(ref, lo, [calls[p] for p in ps], flanking, max_co, args.disable_read_start_end_filtering)
+        text = mpileup_text(args, ctg_name, lo, hi, ps, flanking)
         return evaluate_job(text, ref, lo, [calls[p] for p in ps], flanking, max_co, args.disable_read_start_end_filtering)
     threads = max(1, int(args.threads * 4 / 5))
     if len(jobs) <= 1 or threads <= 1:
@@ -334,6 +435,10 @@ def build_parser():
     p.add_argument("--show_ref", action="store_true")
     p.add_argument("--samtools", type=str, default="samtools")
     p.add_argument("--mpileup_fn", type=str, default=None, help="prepared nine-column mpileup text instead of running samtools")
+    p.add_argument("--pileup_source", choices=("samtools", "bam"), default="samtools",
+                   help="bam: the calls' windows are piled up from the BAM itself (cto_hap_windows), no samtools and no text; --mpileup_fn wins")
+    p.add_argument("--where", choices=("device", "host"), default=None, help="for --pileup_source bam; default: device when a GPU is present")
+    p.add_argument("--bai_fn", type=str, default=None, help="for --pileup_source bam; default: <bam>.bai")
     p.add_argument("--apply_haplotype_filtering", type=str2bool, default=True)
     p.add_argument("--min_mq", type=int, default=20)             # shared/param.py:17
     p.add_argument("--min_bq", type=int, default=0)              # shared/param.py:19

@@ -561,6 +561,60 @@ int cto_haplotype_filter(const char* text, size_t len, const char* ref_seq, int6
                          const int32_t* pos, const char* fields, const int64_t* field_off, const double* af, int flanking,
                          int max_co_exist_read_num, int disable_rse, uint8_t* flags, int64_t* strand);
 
+/* The same in its two halves, with the job object between them: a producer builds the job - cto_hap_job_from_text from the rows of
+ * the nine-column text whose position lies in [lo, hi] (cto_haplotype_filter takes min(pos) - flanking, clipped at 1, and
+ * max(pos) + flanking), cto_hap_windows (below) from the BAM itself - and cto_hap_evaluate applies the per-call rules to it, with
+ * cto_haplotype_filter's arguments.  cto_haplotype_filter is from_text, evaluate and free in a row.  A job is read-only once built:
+ * several threads may evaluate it. */
+int  cto_hap_job_from_text(const char* text, size_t len, int64_t lo, int64_t hi, void** job);
+int  cto_hap_evaluate(const void* job, const char* ref_seq, int64_t region_lo, size_t ref_len, int64_t n, const int32_t* pos,
+                      const char* fields, const int64_t* field_off, const double* af, int flanking, int max_co_exist_read_num,
+                      int disable_rse, uint8_t* flags, int64_t* strand);
+void cto_hap_job_free(void* job);
+
+/* A job's own storage, for tests and for a later evaluation on the device: columns in ascending position, CSR.  The records of
+ * column c are recs[col_off[c] .. col_off[c + 1]), in the order the text lists them (file order of the reads); rse[rse_off[c] ..
+ * rse_off[c + 1]) are the record indices of its read start / end set (ascending; -1 = "the last record", as the reference's
+ * Python index).  The pointers live as long as the job. */
+typedef struct cto_hap_rec {
+    int32_t read;                 /* id of the key "<qname>_<0|1>" (cto_hap_job_key_string); the suffix is 1 iff the base printed in
+                                   * lower case or as '#' */
+    int32_t indel_off, indel_len; /* into `indels`: sign and sequence as printed (case kept, no digits); 0 / 0 when none */
+    int32_t joined;               /* id of upper(base + indel), the key of the column's Counter */
+    int32_t bq, mq;
+    uint8_t base;                 /* upper-cased: A C G T N * # */
+    uint8_t hp;                   /* first character of the HP field ('1', '2'; anything else, '*' included, is untagged) */
+    uint8_t hp_single;            /* the HP field is exactly one character */
+    uint8_t pad_;
+} cto_hap_rec;
+typedef struct cto_hap_view {
+    int64_t n_cols, n_recs, n_reads, n_rse, indel_bytes, lo, hi;
+    const int64_t *col_pos, *col_off, *rse_off;
+    const cto_hap_rec* recs;
+    const int32_t* rse;
+    const char* indels;
+} cto_hap_view;
+int  cto_hap_job_view(const void* job, cto_hap_view* view);
+int  cto_hap_job_key_string(const void* job, int64_t read, const char** s);                  /* NUL-terminated, owned by the job */
+
+/* The job of the calls' windows from the BAM, without text (csrc/hapwindows.hip: the rules in full, the device path; csrc/bam.cpp:
+ * the host rules): what cto_hap_job_from_text would build from
+ *   samtools mpileup --min-MQ q --min-BQ q --excl-flags F [-l bed] -r ctg:lo-hi --output-MQ --output-QNAME --output-extra HP
+ * PARITY UNPINNED against samtools, like every BAM reader here.
+ *   region_lo, region_hi     1-based, inclusive (-r); the job spans exactly them
+ *   iv, n_iv                 0-based [s, e) pairs, ascending and disjoint (-l); NULL = every position of the region
+ *   max_depth                samtools' -d (8000 by default; 0 = no cap); reverse_del: print a reverse-strand deletion as '#'
+ *   where                    0 host, 1 device - as cto_af_tallies takes it; the two build the same job, byte for byte
+ *   stats                    may be NULL.  fallback_chunks: chunks redone on the host because they did not inflate, failed a CRC-32
+ *                            or had a broken record chain; cap_chunks: chunks redone there because the depth cap came into play;
+ *                            host_columns: single columns rebuilt there (a reference skip covers them). */
+typedef struct cto_hap_stats { int64_t n_chunks, n_reads_entered, n_blocks, inflated_bytes, fallback_chunks, cap_chunks, host_columns,
+                                       n_cols, n_recs;
+                               double ms_read, ms_inflate, ms_records, ms_kernels, ms_down, ms_build; } cto_hap_stats;
+int cto_hap_windows(const char* bam_path, const char* bai_path, const char* ctg_name, int64_t region_lo, int64_t region_hi,
+                    const int64_t* iv, int64_t n_iv, int min_mq, int min_bq, int excl_flags, int max_depth, int reverse_del, int where,
+                    void** job, cto_hap_stats* stats);
+
 /* ------------------------------------------------------------------------------------------------
  * Illumina realignment filter (SURVEY.md 8f #4b; src/realign_variants.py, src/realign_reads.py, the C++ under src/realign/).
  * Host code: ~1 k low-QUAL calls per run, a window of <= 1000 reads each.
