@@ -34,25 +34,35 @@ namespace cto {
 __host__ __device__ constexpr int emb_ps(int cin) { return cin > 0 ? ((cin - 4 + 15) / 16) * 16 + 4 : 0; }
 __host__ __device__ constexpr int emb_kch(int cin) { return (3 * emb_ps(cin) + 15) / 16; }
 
-template <int C, int W, int WKV, int TS>
+// FOLD (cvt_block.h: k_cvt_block): the attention runs on the folded per-head matrices, q_h is C wide and k_h = v_h = the ykv tile itself,
+// so the k and v tiles do not exist (KV_FLOATS = 0: OFF_K = OFF_V = OFF_END) and the q tile [MT*16][C + 4] is exactly the LayerNorm
+// staging tile it doubles as.
+// ECIN (FOLD only): channels of the stage input whose tile the launch's first block stages in the free LDS - a folded narrow stage
+// has less of it than that tile needs, so TOTAL grows to hold it.
+template <int C, int W, int WKV, int TS, bool FOLD = false, int ECIN = 0>
 struct CvtBlockGeom {
+    static_assert(!FOLD || C <= 64, "folding pays only where C <= dim_head");
     static constexpr int R = TS * W, RKV = TS * WKV;
     static constexpr int MT = (R + 15) / 16, MTKV = (RKV + 15) / 16;
-    static constexpr int RS = C + 4, QS = 68, HC = (4 * C < 128 ? 4 * C : 128), US = HC + 4;
+    static constexpr int AW = FOLD ? C : 64;                   // width of one head's q (and k, v) rows
+    static constexpr int RS = C + 4, QS = AW + 4, HC = (4 * C < 128 ? 4 * C : 128), US = HC + 4;
+    static constexpr int KV_FLOATS = FOLD ? 0 : MTKV * 16 * QS;
     static constexpr int OFF_Y = 0;                            // h -> yq -> y (FFN input) -> h'' : [MT*16][RS]
     static constexpr int OFF_YKV = OFF_Y + MT * 16 * RS;       // [MTKV*16][RS]
     static constexpr int OFF_Q = OFF_YKV + MTKV * 16 * RS;     // q_h, then o_h : [MT*16][QS]
     static constexpr int OFF_K = OFF_Q + MT * 16 * QS;
-    static constexpr int OFF_V = OFF_K + MTKV * 16 * QS;
-    static constexpr int OFF_END = OFF_V + MTKV * 16 * QS;
+    static constexpr int OFF_V = OFF_K + KV_FLOATS;
+    static constexpr int OFF_END = OFF_V + KV_FLOATS;
     static constexpr int SCRATCH = OFF_END - OFF_YKV;          // ykv|q|k|v region, re-used for the FFN hidden chunk
     static constexpr int U_FLOATS = MT * 16 * US;
-    static constexpr int TOTAL = OFF_END + (U_FLOATS > SCRATCH ? U_FLOATS - SCRATCH : 0);
+    static constexpr int emb_floats(int cin) { return (MT * 32 + 4) * emb_ps(cin); }
+    static constexpr int TOTAL_BLK = OFF_END + (U_FLOATS > SCRATCH ? U_FLOATS - SCRATCH : 0);
+    static constexpr int TOTAL_EMB = FOLD && ECIN > 0 ? OFF_YKV + emb_floats(ECIN) : 0;
+    static constexpr int TOTAL = TOTAL_BLK > TOTAL_EMB ? TOTAL_BLK : TOTAL_EMB;
     static constexpr size_t LDS_BYTES = size_t(TOTAL) * sizeof(float);
     static constexpr int TMP_FLOATS = OFF_END - OFF_Q;         // q|k|v region doubles as the [MT*16][RS] LayerNorm staging tile
     static constexpr int ALIAS = TOTAL - OFF_YKV;              // everything but sy is free in phases 0 and 8
     static constexpr int KCH1 = (W * RS + 15) / 16;            // fc1 over the LDS image of one site's [W][RS] rows
-    static constexpr int emb_floats(int cin) { return (MT * 32 + 4) * emb_ps(cin); }
     static constexpr bool HEAD_OK = (TS == 16) && (64 + head_lds_floats(6) <= ALIAS);
 };
 
@@ -127,9 +137,22 @@ __device__ __forceinline__ void gemm_span_split(const TileSpan& sp, const float*
 // Workgroups of this geometry that fit one CU's 160 KB of LDS (at most 3 are asked for): the register budget follows from
 // it through __launch_bounds__ (w = minimum waves per SIMD = 2 per resident 512-thread workgroup), otherwise a kernel that
 // fits the LDS twice still runs alone because it was given 132+ registers.
-template <int C, int W, int WKV, int TS>
+template <int C, int W, int WKV, int TS, bool FOLD = false, int ECIN = 0>
 __host__ __device__ constexpr int cvt_blocks_per_cu() {
-    return CvtBlockGeom<C, W, WKV, TS>::LDS_BYTES * 3 <= 160 * 1024 ? 3 : (CvtBlockGeom<C, W, WKV, TS>::LDS_BYTES * 2 <= 160 * 1024 ? 2 : 1);
+    using G = CvtBlockGeom<C, W, WKV, TS, FOLD, ECIN>;
+    // a folded narrow stage would fit three times, but on a third of the registers (80) the kernel spills: two at the most
+    return G::LDS_BYTES * 3 <= 160 * 1024 && !FOLD ? 3 : (G::LDS_BYTES * 2 <= 160 * 1024 ? 2 : 1);
+}
+
+// sum over the N-lane group (N = 4, 8 or 16 consecutive lanes of a 16-lane row) this lane belongs to, in every lane of it
+template <int N>
+__device__ __forceinline__ float rowN_sum(float v) {
+    static_assert(N == 4 || N == 8 || N == 16, "a quad, half a DPP row or a DPP row");
+    v += dpp_mov<0xB1>(v);                            // quad_perm [1,0,3,2]
+    v += dpp_mov<0x4E>(v);                            // quad_perm [2,3,0,1]
+    if constexpr (N >= 8) v += dpp_mov<0x141>(v);     // row_half_mirror: the other quad of the half row
+    if constexpr (N >= 16) v += dpp_mov<0x140>(v);    // row_mirror: the other half row
+    return v;
 }
 
 // SPLIT (experiment, side channel: CTO_CVT_SPLIT=f16|bf16; 0 = the fp32 product kernel, 1 = f16, 2 = bf16): the five weight GEMMs
@@ -137,10 +160,19 @@ __host__ __device__ constexpr int cvt_blocks_per_cu() {
 // written as [hi | lo] rows by the phase that produces them (depth-wise conv + BN, attention, second LayerNorm, GELU epilogue)
 // at the fp32 row pitch, the weights come pre-split.  The residual stream, LayerNorm, softmax, the embedding and the classifier
 // are unchanged fp32.
-template <int C, int W, int WKV, int TS, int CIN, bool HEAD, int SPLIT = 0>
-__global__ __launch_bounds__(CVT_BLOCK_THREADS, (2 * cvt_blocks_per_cu<C, W, WKV, TS>())) void k_cvt_block(float* __restrict__ h, CvtStageParams sp,
-                                                                                                            HeadTailParams hp, int heads, int B) {
-    using G = CvtBlockGeom<C, W, WKV, TS>;
+//
+// FOLD (C <= 64, SPLIT == 0; CTO_CVT_FOLD=0 selects the unfolded kernel): to_q, to_k and to_v have no bias, so for one head
+//   scores_h = (yq Wq_h^T)(ykv Wk_h^T)^T = (yq Mq_h) ykv^T,                    Mq_h = Wq_h^T Wk_h    [C x C]
+//   out     += softmax(scores_h / 8) (ykv Wv_h^T) Wo_h^T = (P_h ykv) Mo_h,     Mo_h = Wv_h^T Wo_h^T  [C x C]
+// with Mq_h, Mo_h formed once when the model handle is created (models.hip: upload_folded).  p.wq then holds the Mq_h (as the
+// [heads * C][C] weight of a C-wide q GEMM), p.wo the Mo_h ([C][heads * C]), p.wkv is not read: the [k_h | v_h] GEMM and its tiles
+// are gone, the softmax reads k rows and v rows from sykv, and the out-projection's K is C per head.  No wider than the q
+// projection and the out-projection they replace where C <= dim_head = 64; at C = 128 it would add work.
+template <int C, int W, int WKV, int TS, int CIN, bool HEAD, int SPLIT = 0, bool FOLD = false>
+__global__ __launch_bounds__(CVT_BLOCK_THREADS, (2 * cvt_blocks_per_cu<C, W, WKV, TS, FOLD, FOLD ? CIN : 0>())) void k_cvt_block(float* __restrict__ h, CvtStageParams sp,
+                                                                                                                  HeadTailParams hp, int heads, int B) {
+    using G = CvtBlockGeom<C, W, WKV, TS, FOLD, FOLD ? CIN : 0>;
+    static_assert(!FOLD || SPLIT == 0, "the folded matrices exist in fp32 only");
     constexpr bool SP = SPLIT != 0, F16 = SPLIT == 1;
     static_assert(!SP || (C % 64 == 0 && MT_EXACT<C, W, WKV, TS>()), "split GEMMs: 32-wide k chunks, 16-byte LayerNorm pieces, no pad rows");
     using WPtr = std::conditional_t<SP, const unsigned short*, const float*>;
@@ -148,10 +180,10 @@ __global__ __launch_bounds__(CVT_BLOCK_THREADS, (2 * cvt_blocks_per_cu<C, W, WKV
     static_assert(!HEAD || G::HEAD_OK, "classifier tail needs a 16-site tile and room for its scratch");
     static_assert(G::MT * 16 * G::RS <= G::TMP_FLOATS, "LayerNorm staging tile does not fit the q|k|v region");
     constexpr int NT = CVT_BLOCK_THREADS, NWV = CVT_WAVES;
-    constexpr int R = G::R, MT = G::MT, MTKV = G::MTKV, RKV = G::RKV, RS = G::RS, QS = G::QS, HC = G::HC, US = G::US;
+    constexpr int R = G::R, MT = G::MT, MTKV = G::MTKV, RKV = G::RKV, RS = G::RS, QS = G::QS, HC = G::HC, US = G::US, AW = G::AW;
     static_assert(C % 16 == 0 && C <= 128 && NT % C == 0, "channel count must be 16, 32, 64 or 128");
     using OC = ColOwn<C>;       // C-wide outputs: embedding, out-projection, second FFN GEMM (= the residual stream's owners)
-    using OQ = ColOwn<64>;      // q of one head
+    using OQ = ColOwn<AW>;      // q of one head
     using OKV = ColOwn<128>;    // [k_h | v_h]
     using OF = ColOwn<HC>;      // one FFN hidden chunk
     constexpr int MGC = MSplit<MT, OC::MSPLIT>::MTG, MGQ = MSplit<MT, OQ::MSPLIT>::MTG, MGF = MSplit<MT, OF::MSPLIT>::MTG;
@@ -161,17 +193,17 @@ __global__ __launch_bounds__(CVT_BLOCK_THREADS, (2 * cvt_blocks_per_cu<C, W, WKV
     float* sy = smem + G::OFF_Y;
     float* sykv = smem + G::OFF_YKV;
     float* sq = smem + G::OFF_Q;
-    float* sk = smem + G::OFF_K;
+    float* sk = smem + G::OFF_K;         // (FOLD: no k / v tiles, never dereferenced)
     float* sv = smem + G::OFF_V;
     float* stmp = smem + G::OFF_Q;       // alias: LayerNorm staging tile [MT*16][RS] (phases 1-2 and 4-5)
     float* su = smem + G::OFF_YKV;       // alias: FFN hidden chunk [MT*16][US]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, kg = lane >> 4;
-    const TileSpan spc = tile_span<C, MT>(wave), spq = tile_span<64, MT>(wave), spf = tile_span<HC, MT>(wave);
+    const TileSpan spc = tile_span<C, MT>(wave), spq = tile_span<AW, MT>(wave), spf = tile_span<HC, MT>(wave);
     const int site0 = blockIdx.x * TS;
     const int nsite = min(TS, B - site0);
     const int rows_valid = nsite * W;
-    const int inner = heads * 64;
+    const int inner = heads * AW;       // k extent of the out-projection
     float* hg = h + int64_t(site0) * W * C;
     int nstamp = 0;
     long long* const prof = sp.blk[0].prof;
@@ -450,10 +482,10 @@ __global__ __launch_bounds__(CVT_BLOCK_THREADS, (2 * cvt_blocks_per_cu<C, W, WKV
         else return w + (int64_t(tile) * kch + c0) * FRAG_CS + 4 * lane;
     };
     constexpr int KD = SP ? 32 : 16;            // k elements per chunk
-    auto q_rows = [&](int hh, WPtr (&wr)[1]) { wr[0] = frag(p.wq, p.wq_s, hh * 4 + spq.tile0, C / KD, 0); };
+    auto q_rows = [&](int hh, WPtr (&wr)[1]) { wr[0] = frag(p.wq, p.wq_s, hh * (AW / 16) + spq.tile0, C / KD, 0); };
     auto o_rows = [&](int hh, WPtr (&wr)[NTC]) {
 #pragma unroll
-        for (int nt = 0; nt < NTC; ++nt) wr[nt] = frag(p.wo, p.wo_s, spc.tile0 + nt, inner / KD, hh * (64 / KD));
+        for (int nt = 0; nt < NTC; ++nt) wr[nt] = frag(p.wo, p.wo_s, spc.tile0 + nt, inner / KD, hh * (AW / KD));
     };
     auto w1_rows = [&](int cc, WPtr (&wr)[NTF]) {
 #pragma unroll
@@ -471,13 +503,14 @@ __global__ __launch_bounds__(CVT_BLOCK_THREADS, (2 * cvt_blocks_per_cu<C, W, WKV
         // 16 (w - 4)..) for all m-tiles
         const int wn = wave & 3;
         WPtr wkv1_r[1] = {frag(p.wkv, p.wkv_s, (wave < 4 ? 0 : inner / 16) + hh * 4 + wn, C / KD, 0)};
-        const auto pre_kv1 = prefetch_b<1, C / KD>(wkv1_r);
-        {   // q_h : [R][64], this wave's 16 columns of its m-tile group
+        decltype(prefetch_b<1, C / KD>(wkv1_r)) pre_kv1;
+        if constexpr (!FOLD) pre_kv1 = prefetch_b<1, C / KD>(wkv1_r);
+        {   // q_h : [R][AW] (FOLD: yq Mq_h), this wave's 16 columns of its m-tile group
             f32x4 aq[MGQ][1];
 #pragma unroll
             for (int mt = 0; mt < MGQ; ++mt) aq[mt][0] = f32x4{0.f, 0.f, 0.f, 0.f};
             if constexpr (SP) gemm_span_split<64, MT, C / 32, F16>(spq, sy, RS, C, wq_r, pre_q, aq, j, kg);
-            else gemm_span<64, MT, C / 16>(spq, sy, RS, wq_r, pre_q, aq, j, kg);
+            else gemm_span<AW, MT, C / 16>(spq, sy, RS, wq_r, pre_q, aq, j, kg);
 #pragma unroll
             for (int mt = 0; mt < MGQ; ++mt)
                 if (mt < spq.mcount) {
@@ -487,8 +520,8 @@ __global__ __launch_bounds__(CVT_BLOCK_THREADS, (2 * cvt_blocks_per_cu<C, W, WKV
         }
         WPtr wo_r[NTC];
         o_rows(hh, wo_r);
-        const auto pre_o = prefetch_b<NTC, 64 / KD>(wo_r);
-        {   // k_h, v_h : [RKV][64] each, one n-tile of the pair per wave, all m-tiles
+        const auto pre_o = prefetch_b<NTC, AW / KD>(wo_r);
+        if constexpr (!FOLD) {   // k_h, v_h : [RKV][64] each, one n-tile of the pair per wave, all m-tiles
             f32x4 akv1[MTKV][1];
 #pragma unroll
             for (int mt = 0; mt < MTKV; ++mt) akv1[mt][0] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -502,30 +535,37 @@ __global__ __launch_bounds__(CVT_BLOCK_THREADS, (2 * cvt_blocks_per_cu<C, W, WKV
         }
         lds_barrier();
         stamp();
-        // softmax(q k^T / 8) v of one query row per 16-lane group (model.py:126-131; dim_head = 64): lane l owns dimensions
-        // 4l .. 4l+3 of q, of every k and v row of the site and of the output, which replaces q in place.  Scores are partial
-        // dots reduced inside the 16-lane row; no score matrix in LDS, no barrier between scores, softmax and P v.
+        // softmax(q k^T / 8) v of one query row per group of LPR = AW / 4 lanes (model.py:126-131; dim_head = 64, so 16 lanes unless
+        // FOLD makes the rows C wide): lane l owns dimensions 4l .. 4l+3 of q, of every k and v row of the site and of the output,
+        // which replaces q in place.  Scores are partial dots reduced inside the lane group; no score matrix in LDS, no barrier
+        // between scores, softmax and P v.  FOLD: the k rows and the v rows are both the site's ykv rows.
 #if CTO_CVT_ABL != 2
         {
-            constexpr int NPA = (R + NT / 16 - 1) / (NT / 16); constexpr int UF = WKV <= 5 ? 2 : 1;
-            const int l4 = (lane & 15) * 4;
+            constexpr int LPR = AW / 4, RPP = NT / LPR;
+            constexpr int NPA = (R + RPP - 1) / RPP; constexpr int UF = WKV <= 5 ? 2 : 1;
+            const int l4 = (lane % LPR) * 4;
 #pragma unroll UF
             for (int q = 0; q < NPA; ++q) {
-                const int row = q * (NT / 16) + (tid >> 4);
+                const int row = q * RPP + tid / LPR;
                 const int rr = row < R ? row : 0;
                 const int s = rr / W;
                 const float4 qv = *reinterpret_cast<const float4*>(sq + rr * QS + l4);
                 float4 kv[WKV], vv[WKV];
 #pragma unroll
                 for (int jj = 0; jj < WKV; ++jj) {
-                    kv[jj] = *reinterpret_cast<const float4*>(sk + (s * WKV + jj) * QS + l4);
-                    vv[jj] = *reinterpret_cast<const float4*>(sv + (s * WKV + jj) * QS + l4);
+                    if constexpr (FOLD) {
+                        kv[jj] = *reinterpret_cast<const float4*>(sykv + (s * WKV + jj) * RS + l4);
+                        vv[jj] = kv[jj];
+                    } else {
+                        kv[jj] = *reinterpret_cast<const float4*>(sk + (s * WKV + jj) * QS + l4);
+                        vv[jj] = *reinterpret_cast<const float4*>(sv + (s * WKV + jj) * QS + l4);
+                    }
                 }
                 float sc[WKV];
 #pragma unroll
                 for (int jj = 0; jj < WKV; ++jj) sc[jj] = fmaf(qv.w, kv[jj].w, fmaf(qv.z, kv[jj].z, fmaf(qv.y, kv[jj].y, qv.x * kv[jj].x)));
 #pragma unroll
-                for (int jj = 0; jj < WKV; ++jj) sc[jj] = row16_sum(sc[jj]);
+                for (int jj = 0; jj < WKV; ++jj) sc[jj] = rowN_sum<LPR>(sc[jj]);
                 float mx = sc[0];
 #pragma unroll
                 for (int jj = 1; jj < WKV; ++jj) mx = fmaxf(mx, sc[jj]);
@@ -554,7 +594,7 @@ __global__ __launch_bounds__(CVT_BLOCK_THREADS, (2 * cvt_blocks_per_cu<C, W, WKV
         lds_barrier();
         stamp();
         if constexpr (SP) gemm_span_split<C, MT, 2, F16>(spc, sq, QS, 64, wo_r, pre_o, acc_o, j, kg);
-        else gemm_span<C, MT, 4>(spc, sq, QS, wo_r, pre_o, acc_o, j, kg);   // acc_o += o_h Wo[:, hh*64 .. +64]^T
+        else gemm_span<C, MT, AW / 16>(spc, sq, QS, wo_r, pre_o, acc_o, j, kg);   // acc_o += o_h Wo[:, hh*64 .. +64]^T  (FOLD: a_h Mo_h)
         lds_barrier();   // sq / sk / sv are rewritten by the next head
         stamp();
     }

@@ -71,6 +71,8 @@ struct BlockDev {
     float *n0g, *n0b, *dwq, *bnq, *wq, *dwkv, *bnkv, *wkv, *wo, *bo, *n1g, *n1b, *w1, *b1, *w2, *b2;
     // the five GEMM weights in fragment order for the fused block kernel (cvt_gemm.h); the row-major ones serve the unfused path
     float *wq_f = nullptr, *wkv_f = nullptr, *wo_f = nullptr, *w1_f = nullptr, *w2_f = nullptr;
+    // folded attention weights of a fused stage with C <= 64 (upload_folded), in the fragment order of wq_f / wo_f, or null
+    float *mq_f = nullptr, *mo_f = nullptr;
     // split-operand experiment (CTO_CVT_SPLIT): (hi, lo) 16-bit fragments per GEMM weight, or null
     float *wq_s = nullptr, *wkv_s = nullptr, *wo_s = nullptr, *w1_s = nullptr, *w2_s = nullptr;
 };
@@ -109,6 +111,7 @@ struct cto_model {
     bool fuse_blocks = true;   // fused transformer-block kernel where the stage geometry allows (CTO_CVT_UNFUSED=1 disables)
     bool fuse_embed = true;    // stage embedding + LayerNorm inside the stage's first block (CTO_CVT_NO_EMBED_FUSE=1 disables)
     bool fuse_head = true;     // fc1 + classifier tail inside the network's last block (CTO_CVT_NO_HEAD_FUSE=1 disables)
+    bool fold = true;          // folded attention weights in the fused stages where they are faster (CTO_CVT_FOLD=0 disables)
     // live kernel timing (cto_model_profile)
     bool prof = false;          // the dominant kernel is bracketed by events
     bool prof_all = false;      // ... and BiGRU layer 1 too (cto_model_profile(m, 2))
@@ -314,13 +317,13 @@ struct BlockExtra {            // what the first / last block of the network add
     int n_out = 0;
 };
 
-template <int C, int W, int WKV, int TS, int CIN, bool HEAD, int SPLIT = 0>
+template <int C, int W, int WKV, int TS, int CIN, bool HEAD, int SPLIT = 0, bool FOLD = false>
 int launch_cvt_block(hipStream_t s, float* h, const BlockDev* blocks, int nblk, int heads, int64_t B, const BlockExtra& ex) {
-    using G = CvtBlockGeom<C, W, WKV, TS>;
+    using G = CvtBlockGeom<C, W, WKV, TS, FOLD, FOLD ? CIN : 0>;
     static_assert(G::LDS_BYTES <= 160 * 1024, "fused CvT block does not fit the 160 KB LDS of a gfx950 CU");
     static bool attr_set = false;
     if (!attr_set) {
-        CTO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cvt_block<C, W, WKV, TS, CIN, HEAD, SPLIT>),
+        CTO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cvt_block<C, W, WKV, TS, CIN, HEAD, SPLIT, FOLD>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, int(G::LDS_BYTES)));
         attr_set = true;
     }
@@ -332,7 +335,8 @@ int launch_cvt_block(hipStream_t s, float* h, const BlockDev* blocks, int nblk, 
     sp.nblk = nblk;
     for (int i = 0; i < nblk; ++i) {
         const BlockDev& b = blocks[i];
-        sp.blk[i] = CvtBlockParams{b.n0g, b.n0b, b.dwq, b.bnq, b.wq_f, b.dwkv, b.bnkv, b.wkv_f, b.wo_f, b.bo, b.n1g, b.n1b, b.w1_f, b.b1, b.w2_f, b.b2,
+        if (FOLD) CTO_REQUIRE(b.mq_f && b.mo_f, CTO_EINVAL, "folded CvT block without folded weights");
+        sp.blk[i] = CvtBlockParams{b.n0g, b.n0b, b.dwq, b.bnq, FOLD ? b.mq_f : b.wq_f, b.dwkv, b.bnkv, FOLD ? nullptr : b.wkv_f, FOLD ? b.mo_f : b.wo_f, b.bo, b.n1g, b.n1b, b.w1_f, b.b1, b.w2_f, b.b2,
                                    prof_on ? prof_buf : nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                                    nullptr, nullptr, nullptr, nullptr, nullptr};
         if (SPLIT != 0) {
@@ -354,24 +358,32 @@ int launch_cvt_block(hipStream_t s, float* h, const BlockDev* blocks, int nblk, 
         p.w1p = ex.head->w1p; p.b1h = ex.head->b1;
         hp = HeadTailParams{ex.head->w2, ex.head->b2, ex.head->w3, ex.head->b3, ex.logits, ex.n_out};
     }
-    hipLaunchKernelGGL((k_cvt_block<C, W, WKV, TS, CIN, HEAD, SPLIT>), dim3(unsigned(cdiv(B, TS))), dim3(CVT_BLOCK_THREADS), G::LDS_BYTES,
+    hipLaunchKernelGGL((k_cvt_block<C, W, WKV, TS, CIN, HEAD, SPLIT, FOLD>), dim3(unsigned(cdiv(B, TS))), dim3(CVT_BLOCK_THREADS), G::LDS_BYTES,
                        s, h, sp, hp, heads, int(B));
     CTO_HIP(hipGetLastError());
     if (prof_on) {   // debug aid: phase time stamps of workgroup 0 (cycles since the kernel's first stamp)
         long long hst[256];
         CTO_HIP(hipStreamSynchronize(s));
         CTO_HIP(hipMemcpy(hst, prof_buf, sizeof(hst), hipMemcpyDeviceToHost));
-        fprintf(stderr, "k_cvt_block<%d,%d,%d,%d,%d,%d> x%d stamps:", C, W, WKV, TS, CIN, int(HEAD), nblk);
+        fprintf(stderr, "k_cvt_block<%d,%d,%d,%d,%d,%d,%d,%d> x%d stamps:", C, W, WKV, TS, CIN, int(HEAD), SPLIT, int(FOLD), nblk);
         for (int i = 1; i < 256 && hst[i]; ++i) fprintf(stderr, " %lld", hst[i] - hst[i - 1]);
         fprintf(stderr, "\n");
     }
     return CTO_OK;
 }
 
+// Fused geometries that run on folded attention weights unless CTO_CVT_FOLD=0: those that measured faster folded -
+// every one with C <= dim_head = 64, where a folded matrix is no larger than the projection it replaces.
+constexpr bool cvt_fold_geom(int c) { return c <= 64; }
+
 // The instantiated geometries: (C, W, WKV) -> sites per workgroup and the stage-input channel count whose embedding
 // can run inside the stage's first block.
-template <int C, int W, int WKV, int TS, int CIN, int SPLIT>
+template <int C, int W, int WKV, int TS, int CIN, int SPLIT, bool FOLD = false>
 int dispatch_block_kind(hipStream_t s, float* h, const BlockDev* blocks, int nblk, int heads, int64_t B, const BlockExtra& ex, bool embed, bool head) {
+    if constexpr (FOLD) {
+        return embed ? launch_cvt_block<C, W, WKV, TS, CIN, false, 0, true>(s, h, blocks, nblk, heads, B, ex)
+                     : launch_cvt_block<C, W, WKV, TS, 0, false, 0, true>(s, h, blocks, nblk, heads, B, ex);
+    }
     if constexpr (C == 128 && CvtBlockGeom<C, W, WKV, TS>::HEAD_OK) {
         if (head) return embed ? launch_cvt_block<C, W, WKV, TS, CIN, true, SPLIT>(s, h, blocks, nblk, heads, B, ex)
                                : launch_cvt_block<C, W, WKV, TS, 0, true, SPLIT>(s, h, blocks, nblk, heads, B, ex);
@@ -382,10 +394,13 @@ int dispatch_block_kind(hipStream_t s, float* h, const BlockDev* blocks, int nbl
 // split (0 = fp32; 1 = f16, 2 = bf16: experiment) exists for the 64- and 128-channel stages with 16-site tiles
 template <int C, int W, int WKV, int TS, int CIN>
 int dispatch_block(hipStream_t s, float* h, const BlockDev* blocks, int nblk, int heads, int64_t B, const BlockExtra& ex, bool embed, bool head,
-                   int split) {
+                   int split, bool fold) {
     if constexpr (C % 64 == 0 && MT_EXACT<C, W, WKV, TS>()) {
         if (split == 1) return dispatch_block_kind<C, W, WKV, TS, CIN, 1>(s, h, blocks, nblk, heads, B, ex, embed, head);
         if (split == 2) return dispatch_block_kind<C, W, WKV, TS, CIN, 2>(s, h, blocks, nblk, heads, B, ex, embed, head);
+    }
+    if constexpr (cvt_fold_geom(C)) {       // the fp32 kernel on folded attention weights (cvt_block.h: FOLD)
+        if (fold && blocks->mq_f) return dispatch_block_kind<C, W, WKV, TS, CIN, 0, true>(s, h, blocks, nblk, heads, B, ex, embed, head);
     }
     return dispatch_block_kind<C, W, WKV, TS, CIN, 0>(s, h, blocks, nblk, heads, B, ex, embed, head);
 }
@@ -414,13 +429,14 @@ bool can_fuse_head(const StageDev& st, const HeadDev& hd) { const FusedGeom* g =
 // nblk consecutive fused transformer blocks of a stage in one launch, when the stage geometry has an instantiation; returns 1 if it
 // ran, 0 if not, < 0 on error
 int try_fused_blocks(hipStream_t s, const StageDev& st, const BlockDev* b, int nblk, float* h, int64_t B, const BlockExtra& ex, bool embed,
-                     bool head, int split) {
+                     bool head, int split, bool fold) {
     int rc = CTO_OK;
     if (!b->wq_s) split = 0;
-    if (st.c == 128 && st.w == 5 && st.wkv == 3) rc = dispatch_block<128, 5, 3, CTO_CVT_TS3, 64>(s, h, b, nblk, st.heads, B, ex, embed, head, split);
-    else if (st.c == 64 && st.w == 9 && st.wkv == 5) rc = dispatch_block<64, 9, 5, CTO_CVT_TS2, 16>(s, h, b, nblk, st.heads, B, ex, embed, head, split);
-    else if (st.c == 16 && st.w == 17 && st.wkv == 9) rc = dispatch_block<16, 17, 9, CTO_CVT_TS1, 34>(s, h, b, nblk, st.heads, B, ex, embed, head, split);
-    else if (st.c == 32 && st.w == 17 && st.wkv == 9) rc = dispatch_block<32, 17, 9, CTO_CVT_TS1, 34>(s, h, b, nblk, st.heads, B, ex, embed, head, split);
+    if (split) fold = false;
+    if (st.c == 128 && st.w == 5 && st.wkv == 3) rc = dispatch_block<128, 5, 3, CTO_CVT_TS3, 64>(s, h, b, nblk, st.heads, B, ex, embed, head, split, fold);
+    else if (st.c == 64 && st.w == 9 && st.wkv == 5) rc = dispatch_block<64, 9, 5, CTO_CVT_TS2, 16>(s, h, b, nblk, st.heads, B, ex, embed, head, split, fold);
+    else if (st.c == 16 && st.w == 17 && st.wkv == 9) rc = dispatch_block<16, 17, 9, CTO_CVT_TS1, 34>(s, h, b, nblk, st.heads, B, ex, embed, head, split, fold);
+    else if (st.c == 32 && st.w == 17 && st.wkv == 9) rc = dispatch_block<32, 17, 9, CTO_CVT_TS1, 34>(s, h, b, nblk, st.heads, B, ex, embed, head, split, fold);
     else return 0;
     return rc == CTO_OK ? 1 : rc;
 }
@@ -458,7 +474,7 @@ int cvt_forward(cto_model* m, const float* x, int64_t B, float* logits, hipStrea
                 const bool head = m->fuse_head && si == 2 && bi + size_t(nblk) == st.blocks.size() && can_fuse_head(st, m->head);
                 ex.xin = in; ex.st = &st; ex.head = &m->head; ex.logits = logits; ex.n_out = m->n_out;
                 ex.raw = (si == 0 && embed) ? raw : nullptr;
-                const int fr = try_fused_blocks(s, st, &b, nblk, hbuf, B, ex, embed, head, m->cvt_split);
+                const int fr = try_fused_blocks(s, st, &b, nblk, hbuf, B, ex, embed, head, m->cvt_split, m->fold);
                 if (fr < 0) return fr;
                 if (fr == 1) {
                     if (head) return CTO_OK;
@@ -653,6 +669,35 @@ int upload_split_fragments(const cto_weights* w, const std::string& name, int nt
             }
     return upload_halves(fr, a, out);
 }
+// Folded attention weights of one block (cvt_block.h: FOLD).  to_q, to_k and to_v have no bias, so per head h, with Wq_h, Wk_h, Wv_h
+// the [64][C] row blocks of to_q / to_kv and Wo_h the [C][64] column block of to_out:
+//   Mq_h = Wq_h^T Wk_h   - stored as the weight [n = h C + c2][k = c1] of the C-wide GEMM  q'_h = yq Mq_h
+//   Mo_h = Wv_h^T Wo_h^T - stored as the weight [n][k = h C + c]       of the GEMM        out += (P_h ykv) Mo_h
+// each formed in double from the fp32 weights and rounded once, then packed like wq_f / wo_f.
+int upload_folded(const cto_weights* w, const std::string& P, int C, int heads, Arena& a, float** mq, float** mo) {
+    int rc = CTO_OK;
+    const int inner = 64 * heads;
+    GETW(wq, P + ".0.fn.to_q.net.2.weight", int64_t(inner) * C);
+    GETW(wkv, P + ".0.fn.to_kv.net.2.weight", int64_t(2) * inner * C);
+    GETW(wo, P + ".0.fn.to_out.0.weight", int64_t(C) * inner);
+    const float* wk = wkv->data();
+    const float* wv = wkv->data() + size_t(inner) * C;
+    std::vector<float> q(size_t(heads) * C * C), o(size_t(C) * heads * C);
+    for (int hh = 0; hh < heads; ++hh)
+        for (int x = 0; x < C; ++x)
+            for (int y = 0; y < C; ++y) {
+                double sq = 0.0, so = 0.0;
+                for (int d = 0; d < 64; ++d) {
+                    const size_t r = size_t(hh) * 64 + d;
+                    sq += double(wk[r * C + x]) * double((*wq)[r * C + y]);              // Mq_h[y][x]
+                    so += double(wv[r * C + y]) * double((*wo)[size_t(x) * inner + r]);   // Mo_h[y][x]
+                }
+                q[(size_t(hh) * C + x) * C + y] = float(sq);
+                o[size_t(x) * heads * C + size_t(hh) * C + y] = float(so);
+            }
+    if ((rc = a.upload(pack_fragments(q.data(), heads * C / 16, C / 16), mq)) != CTO_OK) return rc;
+    return a.upload(pack_fragments(o.data(), C / 16, heads * C / 16), mo);
+}
 int upload_fragments(const cto_weights* w, const std::string& name, int ntiles, int kch, Arena& a, float** out) {
     int rc = CTO_OK;
     GETW(v, name, int64_t(ntiles) * 16 * kch * 16);
@@ -812,6 +857,7 @@ extern "C" int cto_cvt_create_ex(const cto_weights* w, const cto_cvt_cfg* cfg, i
                 (rc = upload_fragments(w, P + ".1.fn.net.0.weight", 4 * NC16, NC16, a, &b.w1_f)) ||
                  (rc = upload_fragments(w, P + ".1.fn.net.3.weight", NC16, 4 * NC16, a, &b.w2_f))))
                 return fail(rc);
+            if (fused_geom(st) && cvt_fold_geom(C) && (rc = upload_folded(w, P, C, st.heads, a, &b.mq_f, &b.mo_f))) return fail(rc);
             if (m->cvt_split && C % 64 == 0) {
                 const bool f16 = m->cvt_split == 1;
                 if ((rc = upload_split_fragments(w, P + ".0.fn.to_q.net.2.weight", NI, C / 32, f16, a, &b.wq_s)) ||
@@ -822,6 +868,8 @@ extern "C" int cto_cvt_create_ex(const cto_weights* w, const cto_cvt_cfg* cfg, i
                     return fail(rc);
             }
             st.blocks.push_back(b);
+            // the reference network's algorithmic count, whatever the kernels issue: the folded path does not run the k | v
+            // projection, and roofline fractions stay comparable with earlier records only if this number does not move
             macs += int64_t(st.w) * C * st.inner + int64_t(st.wkv) * C * 2 * st.inner + int64_t(st.w) * st.inner * C +
                     int64_t(st.w) * 8 * C * C + int64_t(2) * st.heads * st.w * st.wkv * 64 +
                     int64_t(3) * C * (st.w + st.wkv);
@@ -854,6 +902,7 @@ extern "C" int cto_cvt_create_ex(const cto_weights* w, const cto_cvt_cfg* cfg, i
     if (const char* e = getenv("CTO_CVT_UNFUSED")) m->fuse_blocks = !(e[0] == '1');
     if (const char* e = getenv("CTO_CVT_NO_EMBED_FUSE")) m->fuse_embed = !(e[0] == '1');
     if (const char* e = getenv("CTO_CVT_NO_HEAD_FUSE")) m->fuse_head = !(e[0] == '1');
+    if (const char* e = getenv("CTO_CVT_FOLD")) m->fold = !(e[0] == '0');
     *out = m.release();
     return CTO_OK;
 }

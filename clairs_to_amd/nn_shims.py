@@ -86,7 +86,8 @@ class _HipNet(nn.Module):
     split_operands = None
 
     def _weights_version(self):
-        return (self.split_operands,) + tuple((k, int(v._version), v.data_ptr()) for k, v in self.state_dict().items())
+        # CTO_CVT_FOLD is read when a handle is created (csrc/models.hip): a handle built under the other setting is not this one's
+        return (self.split_operands, os.environ.get("CTO_CVT_FOLD")) + tuple((k, int(v._version), v.data_ptr()) for k, v in self.state_dict().items())
 
     def _handle(self, slot="_cto_state"):
         """the C-ABI model handle of this module's current weights (rebuilt when they change).  A handle's activation workspace
