@@ -12,6 +12,7 @@
 //   phase 2  yq = BN(DW_s1(t)) -> sy, ykv = BN(DW_s2(t)) -> sykv                     (model.py:91-100, 112-113)
 //   phase 3  per head: q_h, k_h, v_h (MFMA) -> LDS; softmax(q_h k_h^T / 8) v_h per query row in ONE pass (16 lanes per
 //            row: partial dots, DPP reductions, softmax in registers, o_h over q_h in place); acc_o += o_h Wo_h^T (MFMA)
+//            (FOLD_KV, below: per head [k'_h | v'_h] (MFMA) -> LDS; softmax(yq k'_h^T / 8) v'_h added to the row's h + bias_o in registers)
 //   phase 4  h' = acc_o -> tmp;  acc_f = h' + bias_2
 //   phase 5  y  = LN(h'; norm1) -> sy
 //   phase 6  per 128-wide chunk of the 4C hidden units: u = GELU(y W1^T + b1) -> LDS, acc_f += u W2^T
@@ -39,18 +40,23 @@ __host__ __device__ constexpr int emb_kch(int cin) { return (3 * emb_ps(cin) + 1
 // staging tile it doubles as.
 // ECIN (FOLD only): channels of the stage input whose tile the launch's first block stages in the free LDS - a folded narrow stage
 // has less of it than that tile needs, so TOTAL grows to hold it.
-template <int C, int W, int WKV, int TS, bool FOLD = false, int ECIN = 0>
+// FOLD_KV: the same matrices applied on the k/v rows instead: per head one GEMM [k'_h | v'_h] = ykv [Mq_h^T | Mo_h] over the RKV strided rows
+// replaces the q GEMM and the out-projection.  The q tile's place holds that [MTKV*16][2C + 4] tile (or the LayerNorm staging tile it doubles
+// as, whichever is larger); no q, k or v tiles.
+constexpr int FOLD_NONE = 0, FOLD_Q = 1, FOLD_KV = 2;
+template <int C, int W, int WKV, int TS, int FOLD = FOLD_NONE, int ECIN = 0>
 struct CvtBlockGeom {
-    static_assert(!FOLD || C <= 64, "folding pays only where C <= dim_head");
+    static_assert(FOLD != FOLD_Q || C <= 64, "folding on the query side pays only where C <= dim_head");
     static constexpr int R = TS * W, RKV = TS * WKV;
     static constexpr int MT = (R + 15) / 16, MTKV = (RKV + 15) / 16;
     static constexpr int AW = FOLD ? C : 64;                   // width of one head's q (and k, v) rows
-    static constexpr int RS = C + 4, QS = AW + 4, HC = (4 * C < 128 ? 4 * C : 128), US = HC + 4;
+    static constexpr int RS = C + 4, QS = FOLD == FOLD_KV ? 2 * C + 4 : AW + 4, HC = (4 * C < 128 ? 4 * C : 128), US = HC + 4;
     static constexpr int KV_FLOATS = FOLD ? 0 : MTKV * 16 * QS;
+    static constexpr int Q_FLOATS = FOLD == FOLD_KV ? (MTKV * QS > MT * RS ? MTKV * 16 * QS : MT * 16 * RS) : MT * 16 * QS;
     static constexpr int OFF_Y = 0;                            // h -> yq -> y (FFN input) -> h'' : [MT*16][RS]
     static constexpr int OFF_YKV = OFF_Y + MT * 16 * RS;       // [MTKV*16][RS]
-    static constexpr int OFF_Q = OFF_YKV + MTKV * 16 * RS;     // q_h, then o_h : [MT*16][QS]
-    static constexpr int OFF_K = OFF_Q + MT * 16 * QS;
+    static constexpr int OFF_Q = OFF_YKV + MTKV * 16 * RS;     // q_h, then o_h : [MT*16][QS]  (FOLD_KV: [k'_h | v'_h] : [MTKV*16][QS])
+    static constexpr int OFF_K = OFF_Q + Q_FLOATS;
     static constexpr int OFF_V = OFF_K + KV_FLOATS;
     static constexpr int OFF_END = OFF_V + KV_FLOATS;
     static constexpr int SCRATCH = OFF_END - OFF_YKV;          // ykv|q|k|v region, re-used for the FFN hidden chunk
@@ -137,7 +143,7 @@ __device__ __forceinline__ void gemm_span_split(const TileSpan& sp, const float*
 // Workgroups of this geometry that fit one CU's 160 KB of LDS (at most 3 are asked for): the register budget follows from
 // it through __launch_bounds__ (w = minimum waves per SIMD = 2 per resident 512-thread workgroup), otherwise a kernel that
 // fits the LDS twice still runs alone because it was given 132+ registers.
-template <int C, int W, int WKV, int TS, bool FOLD = false, int ECIN = 0>
+template <int C, int W, int WKV, int TS, int FOLD = FOLD_NONE, int ECIN = 0>
 __host__ __device__ constexpr int cvt_blocks_per_cu() {
     using G = CvtBlockGeom<C, W, WKV, TS, FOLD, ECIN>;
     // a folded narrow stage would fit three times, but on a third of the registers (80) the kernel spills: two at the most
@@ -168,12 +174,21 @@ __device__ __forceinline__ float rowN_sum(float v) {
 // [heads * C][C] weight of a C-wide q GEMM), p.wo the Mo_h ([C][heads * C]), p.wkv is not read: the [k_h | v_h] GEMM and its tiles
 // are gone, the softmax reads k rows and v rows from sykv, and the out-projection's K is C per head.  No wider than the q
 // projection and the out-projection they replace where C <= dim_head = 64; at C = 128 it would add work.
-template <int C, int W, int WKV, int TS, int CIN, bool HEAD, int SPLIT = 0, bool FOLD = false>
+//
+// FOLD_KV (every C, SPLIT == 0; CTO_CVT_FOLD=kv, and the default where it measured fastest - models.hip: cvt_fold_default): the same
+// identity associated the other way, onto the RKV = TS * WKV strided k/v rows instead of the R = TS * W query rows:
+//   scores_h = yq (ykv Mq_h^T)^T = yq k'_h^T,             k'_h = ykv Mq_h^T   [RKV x C]
+//   out      = sum_h P_h (ykv Mo_h) + b_o = sum_h P_h v'_h + b_o,   v'_h = ykv Mo_h     [RKV x C]
+// One GEMM per head, [k'_h | v'_h] = ykv [Mq_h^T | Mo_h] (M = RKV, K = C, N = 2C; p.wkv holds the [heads][2C][C] weights, p.wq and p.wo
+// are not read), replaces the q GEMM, the k|v GEMM and the out-projection.  The q operand of the scores is the yq row itself, P_h v'_h is
+// C wide and already in model space: it is summed over the heads in the query row's registers on top of h + b_o, and reaches the second
+// FFN GEMM's accumulators through the LayerNorm staging tile.  Two barriers per head instead of three, no q tile, no acc_o.
+template <int C, int W, int WKV, int TS, int CIN, bool HEAD, int SPLIT = 0, int FOLD = FOLD_NONE>
 __global__ __launch_bounds__(CVT_BLOCK_THREADS, (2 * cvt_blocks_per_cu<C, W, WKV, TS, FOLD, FOLD ? CIN : 0>())) void k_cvt_block(float* __restrict__ h, CvtStageParams sp,
                                                                                                                   HeadTailParams hp, int heads, int B) {
     using G = CvtBlockGeom<C, W, WKV, TS, FOLD, FOLD ? CIN : 0>;
     static_assert(!FOLD || SPLIT == 0, "the folded matrices exist in fp32 only");
-    constexpr bool SP = SPLIT != 0, F16 = SPLIT == 1;
+    constexpr bool SP = SPLIT != 0, F16 = SPLIT == 1, KVF = FOLD == FOLD_KV;
     static_assert(!SP || (C % 64 == 0 && MT_EXACT<C, W, WKV, TS>()), "split GEMMs: 32-wide k chunks, 16-byte LayerNorm pieces, no pad rows");
     using WPtr = std::conditional_t<SP, const unsigned short*, const float*>;
     static_assert(CIN == 0 || G::emb_floats(CIN) <= G::ALIAS, "stage input tile does not fit the free LDS");
@@ -192,18 +207,15 @@ __global__ __launch_bounds__(CVT_BLOCK_THREADS, (2 * cvt_blocks_per_cu<C, W, WKV
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* sy = smem + G::OFF_Y;
     float* sykv = smem + G::OFF_YKV;
-    float* sq = smem + G::OFF_Q;
-    float* sk = smem + G::OFF_K;         // (FOLD: no k / v tiles, never dereferenced)
-    float* sv = smem + G::OFF_V;
+    float* sq = smem + G::OFF_Q;         // (FOLD_KV: the [k'_h | v'_h] tile)
     float* stmp = smem + G::OFF_Q;       // alias: LayerNorm staging tile [MT*16][RS] (phases 1-2 and 4-5)
     float* su = smem + G::OFF_YKV;       // alias: FFN hidden chunk [MT*16][US]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, kg = lane >> 4;
-    const TileSpan spc = tile_span<C, MT>(wave), spq = tile_span<AW, MT>(wave), spf = tile_span<HC, MT>(wave);
+    const TileSpan spc = tile_span<C, MT>(wave), spf = tile_span<HC, MT>(wave);
     const int site0 = blockIdx.x * TS;
     const int nsite = min(TS, B - site0);
     const int rows_valid = nsite * W;
-    const int inner = heads * AW;       // k extent of the out-projection
     float* hg = h + int64_t(site0) * W * C;
     int nstamp = 0;
     long long* const prof = sp.blk[0].prof;
@@ -404,8 +416,29 @@ __global__ __launch_bounds__(CVT_BLOCK_THREADS, (2 * cvt_blocks_per_cu<C, W, WKV
     for (int bi = 0; bi < sp.nblk; ++bi) {
     const CvtBlockParams& p = sp.blk[bi];
     stamp();
-    // ---- phase 1: the residual stream moves into the out-projection's accumulators; LayerNorm -> staging tile ----
-    f32x4 acc_o[MGC][NTC];
+    // ---- phase 1: the residual stream moves into the out-projection's accumulators (FOLD_KV: into the attention's row registers);
+    //      LayerNorm -> staging tile ----
+    f32x4 acc_o[KVF ? 1 : MGC][NTC];     // (FOLD_KV: no out-projection, not used)
+    // FOLD_KV: no out-projection.  The residual stream waits for the attention in the layout of the attention's own output: a group of
+    // LPK lanes per row, lane l of it owning channels 4l .. 4l+3 of every 64-channel slice (NVK slices), NPK passes over the MT*16 rows
+    // (rows past R carry h + bias_o through unchanged).  sy holds h here for every block of the launch (phase 7 wrote it).
+    constexpr int NVK = C > 64 ? C / 64 : 1, LPK = C / (4 * NVK), RPK = NT / LPK, NPK = (MT * 16 + RPK - 1) / RPK;
+    static_assert(!KVF || (C % (4 * NVK) == 0 && (LPK == 4 || LPK == 8 || LPK == 16)), "attention lane groups: a quad, half a DPP row or a DPP row");
+    const int l4k = (tid % LPK) * 4, rowk = tid / LPK;
+    float4 ho[KVF ? NPK : 1][NVK];
+    if constexpr (KVF) {
+#pragma unroll
+        for (int u = 0; u < NVK; ++u) {
+            const float* bp = p.bo + l4k + 64 * u;
+            const float4 b4 = make_float4(bp[0], bp[1], bp[2], bp[3]);
+#pragma unroll
+            for (int q = 0; q < NPK; ++q) {
+                const int rr = min(q * RPK + rowk, MT * 16 - 1);
+                const float4 h4 = *reinterpret_cast<const float4*>(sy + rr * RS + l4k + 64 * u);
+                ho[q][u] = make_float4(h4.x + b4.x, h4.y + b4.y, h4.z + b4.z, h4.w + b4.w);
+            }
+        }
+    } else {
 #pragma unroll
     for (int nt = 0; nt < NTC; ++nt) {
         const int col = (spc.tile0 + nt) * 16 + j;
@@ -421,6 +454,7 @@ __global__ __launch_bounds__(CVT_BLOCK_THREADS, (2 * cvt_blocks_per_cu<C, W, WKV
                 for (int r = 0; r < 4; ++r) acc_o[mt][nt][r] = acc_f[mt][nt][r] + bv;
             }
         }
+    }
     }
     layer_norm(sy, stmp, p.n0g, p.n0b, std::false_type{});
     lds_barrier();
@@ -482,11 +516,6 @@ __global__ __launch_bounds__(CVT_BLOCK_THREADS, (2 * cvt_blocks_per_cu<C, W, WKV
         else return w + (int64_t(tile) * kch + c0) * FRAG_CS + 4 * lane;
     };
     constexpr int KD = SP ? 32 : 16;            // k elements per chunk
-    auto q_rows = [&](int hh, WPtr (&wr)[1]) { wr[0] = frag(p.wq, p.wq_s, hh * (AW / 16) + spq.tile0, C / KD, 0); };
-    auto o_rows = [&](int hh, WPtr (&wr)[NTC]) {
-#pragma unroll
-        for (int nt = 0; nt < NTC; ++nt) wr[nt] = frag(p.wo, p.wo_s, spc.tile0 + nt, inner / KD, hh * (AW / KD));
-    };
     auto w1_rows = [&](int cc, WPtr (&wr)[NTF]) {
 #pragma unroll
         for (int nt = 0; nt < NTF; ++nt) wr[nt] = frag(p.w1, p.w1_s, cc * (HC / 16) + spf.tile0 + nt, C / KD, 0);
@@ -494,6 +523,122 @@ __global__ __launch_bounds__(CVT_BLOCK_THREADS, (2 * cvt_blocks_per_cu<C, W, WKV
     auto w2_rows = [&](int cc, WPtr (&wr)[NTC]) {
 #pragma unroll
         for (int nt = 0; nt < NTC; ++nt) wr[nt] = frag(p.w2, p.w2_s, spc.tile0 + nt, 4 * C / KD, cc * (HC / KD));
+    };
+    if constexpr (KVF) {
+        // FOLD_KV, per head: [k'_h | v'_h] = ykv [Mq_h^T | Mo_h] (p.wkv: [heads][2C][C] in fragment order) -> skv, barrier, then per query
+        // row softmax(yq . k'_h / 8) v'_h added to the residual row in registers, barrier.  The q operand is the yq row itself, the same for
+        // every head.
+        using OK = ColOwn<2 * C>;
+        constexpr int NTK = OK::NTW, MGK = MSplit<MTKV, OK::MSPLIT>::MTG;
+        const TileSpan spk = tile_span<2 * C, MTKV>(wave);
+        float* skv = sq;                                    // [MTKV*16][QS], QS = 2C + 4: k'_h in columns 0 .. C, v'_h in C .. 2C
+        auto kv_rows = [&](int hh, WPtr (&wr)[NTK]) {
+#pragma unroll
+            for (int nt = 0; nt < NTK; ++nt) wr[nt] = frag(p.wkv, p.wkv_s, hh * (2 * C / 16) + spk.tile0 + nt, C / KD, 0);
+        };
+        WPtr wk_r[NTK];
+        kv_rows(0, wk_r);
+        auto pre_k = prefetch_b<NTK, C / KD>(wk_r);
+        float4 qv[NPK][NVK];
+#pragma unroll
+        for (int q = 0; q < NPK; ++q) {
+            const int row = q * RPK + rowk, rr = row < R ? row : 0;
+#pragma unroll
+            for (int u = 0; u < NVK; ++u) qv[q][u] = *reinterpret_cast<const float4*>(sy + rr * RS + l4k + 64 * u);
+        }
+        for (int hh = 0; hh < heads; ++hh) {
+            {
+                f32x4 ak[MGK][NTK];
+#pragma unroll
+                for (int mt = 0; mt < MGK; ++mt)
+#pragma unroll
+                    for (int nt = 0; nt < NTK; ++nt) ak[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+                gemm_span<2 * C, MTKV, C / 16>(spk, sykv, RS, wk_r, pre_k, ak, j, kg);
+#pragma unroll
+                for (int nt = 0; nt < NTK; ++nt)
+#pragma unroll
+                    for (int mt = 0; mt < MGK; ++mt)
+                        if (mt < spk.mcount) {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) skv[((spk.mbase + mt) * 16 + 4 * kg + r) * QS + (spk.tile0 + nt) * 16 + j] = ak[mt][nt][r];
+                        }
+            }
+            if (hh + 1 < heads) {        // the next head's weights fly under the barrier and the attention
+                kv_rows(hh + 1, wk_r);
+                pre_k = prefetch_b<NTK, C / KD>(wk_r);
+            }
+            lds_barrier();
+            stamp();
+#if CTO_CVT_ABL != 2
+#pragma unroll
+            for (int q = 0; q < NPK; ++q) {
+                const int row = q * RPK + rowk, rr = row < R ? row : 0;
+                const float* kb = skv + (rr / W) * WKV * QS + l4k;
+                float4 kv[WKV][NVK], vv[WKV][NVK];
+#pragma unroll
+                for (int jj = 0; jj < WKV; ++jj)
+#pragma unroll
+                    for (int u = 0; u < NVK; ++u) kv[jj][u] = *reinterpret_cast<const float4*>(kb + jj * QS + 64 * u);
+                float sc[WKV];
+#pragma unroll
+                for (int jj = 0; jj < WKV; ++jj) {
+                    sc[jj] = fmaf(qv[q][0].w, kv[jj][0].w, fmaf(qv[q][0].z, kv[jj][0].z, fmaf(qv[q][0].y, kv[jj][0].y, qv[q][0].x * kv[jj][0].x)));
+#pragma unroll
+                    for (int u = 1; u < NVK; ++u)
+                        sc[jj] = fmaf(qv[q][u].w, kv[jj][u].w, fmaf(qv[q][u].z, kv[jj][u].z, fmaf(qv[q][u].y, kv[jj][u].y, fmaf(qv[q][u].x, kv[jj][u].x, sc[jj]))));
+                }
+                if constexpr (WKV > 5) {        // many rows on a small register budget (stage 1): the v' rows are requested when the k' rows are spent
+#pragma unroll
+                    for (int jj = 0; jj < WKV; ++jj) asm volatile("" : "+v"(sc[jj]));
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+#pragma unroll
+                for (int jj = 0; jj < WKV; ++jj)
+#pragma unroll
+                    for (int u = 0; u < NVK; ++u) vv[jj][u] = *reinterpret_cast<const float4*>(kb + jj * QS + C + 64 * u);
+#pragma unroll
+                for (int jj = 0; jj < WKV; ++jj) sc[jj] = rowN_sum<LPK>(sc[jj]);
+                float mx = sc[0];
+#pragma unroll
+                for (int jj = 1; jj < WKV; ++jj) mx = fmaxf(mx, sc[jj]);
+                float sum = 0.f;
+#pragma unroll
+                for (int jj = 0; jj < WKV; ++jj) { sc[jj] = exp_le0((sc[jj] - mx) * 0.125f); sum += sc[jj]; }
+                float inv = rcp_fast(sum);
+                inv = fmaf(fmaf(-sum, inv, 1.0f), inv, inv);      // one Newton step: 0.5 ulp
+                if (row >= R) inv = 0.f;                          // pad rows keep h + bias_o
+#pragma unroll
+                for (int jj = 0; jj < WKV; ++jj) {
+                    const float pj = sc[jj] * inv;
+#pragma unroll
+                    for (int u = 0; u < NVK; ++u) {
+                        ho[q][u].x = fmaf(pj, vv[jj][u].x, ho[q][u].x); ho[q][u].y = fmaf(pj, vv[jj][u].y, ho[q][u].y);
+                        ho[q][u].z = fmaf(pj, vv[jj][u].z, ho[q][u].z); ho[q][u].w = fmaf(pj, vv[jj][u].w, ho[q][u].w);
+                    }
+                }
+                // The passes are unrolled (ho[q] are registers) and nothing in this loop needs a pass's sums: left alone, the compiler
+                // sinks the softmax and the P v' sums of EVERY pass below the barrier that ends the head (into the block that joins the
+                // time-stamp branch), holding all their k' / v' rows in registers until then, and spills.  The empty statement needs the
+                // sums here; the fence keeps the next passes' row requests behind it - two passes in flight where the rows are few, as
+                // in the other forms.
+#pragma unroll
+                for (int u = 0; u < NVK; ++u) asm volatile("" : "+v"(ho[q][u].x), "+v"(ho[q][u].y), "+v"(ho[q][u].z), "+v"(ho[q][u].w));
+                if ((q + 1) % (WKV <= 5 ? 2 : 1) == 0) __builtin_amdgcn_sched_barrier(0);
+            }
+#endif
+            lds_barrier();   // skv is rewritten by the next head (after the last one: by the hand-over below)
+            stamp();
+        }
+    } else {
+    // unfolded and q-side forms: q GEMM, (k|v GEMM,) attention over the q tile in place, out-projection
+    const TileSpan spq = tile_span<AW, MT>(wave);
+    const int inner = heads * AW;       // k extent of the out-projection
+    float* sk = smem + G::OFF_K;         // (FOLD_Q: no k / v tiles, never dereferenced)
+    float* sv = smem + G::OFF_V;
+    auto q_rows = [&](int hh, WPtr (&wr)[1]) { wr[0] = frag(p.wq, p.wq_s, hh * (AW / 16) + spq.tile0, C / KD, 0); };
+    auto o_rows = [&](int hh, WPtr (&wr)[NTC]) {
+#pragma unroll
+        for (int nt = 0; nt < NTC; ++nt) wr[nt] = frag(p.wo, p.wo_s, spc.tile0 + nt, inner / KD, hh * (AW / KD));
     };
     WPtr wq_r[1];
     q_rows(0, wq_r);
@@ -598,6 +743,7 @@ __global__ __launch_bounds__(CVT_BLOCK_THREADS, (2 * cvt_blocks_per_cu<C, W, WKV
         lds_barrier();   // sq / sk / sv are rewritten by the next head
         stamp();
     }
+    }
 
     // first FFN weights are requested before the residual hand-over and the second LayerNorm
     WPtr w1_r[NTF];
@@ -605,22 +751,40 @@ __global__ __launch_bounds__(CVT_BLOCK_THREADS, (2 * cvt_blocks_per_cu<C, W, WKV
     auto pre_w1 = prefetch_b<NTF, C / KD>(w1_r);
 
     // ---- phase 4: h' = h + to_out(o) + bias sits in acc_o: a copy -> staging tile for the LayerNorm, and h' + b2 seeds the
-    //      second FFN GEMM's accumulators ----
+    //      second FFN GEMM's accumulators (FOLD_KV: h' sits in the attention's row registers and reaches the accumulators through
+    //      the staging tile, which lies over skv - every wave is past the last head's attention) ----
+    if constexpr (KVF) {
+#pragma unroll
+        for (int q = 0; q < NPK; ++q) {
+            const int row = q * RPK + rowk;
+            if (row < MT * 16) {
+#pragma unroll
+                for (int u = 0; u < NVK; ++u) *reinterpret_cast<float4*>(stmp + row * RS + l4k + 64 * u) = ho[q][u];
+            }
+        }
+        lds_barrier();
+    }
 #pragma unroll
     for (int nt = 0; nt < NTC; ++nt) {
         const int col = (spc.tile0 + nt) * 16 + j;
         const float bv = p.b2[col];
 #pragma unroll
         for (int mt = 0; mt < MGC; ++mt) {
-            if (mt < spc.mcount) {
+            if constexpr (KVF) {
+                const int row0 = (spc.mbase + (mt < spc.mcount ? mt : 0)) * 16 + 4 * kg;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) stmp[((spc.mbase + mt) * 16 + 4 * kg + r) * RS + col] = acc_o[mt][nt][r];
+                for (int r = 0; r < 4; ++r) acc_f[mt][nt][r] = stmp[(row0 + r) * RS + col] + bv;
+            } else {
+                if (mt < spc.mcount) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) stmp[((spc.mbase + mt) * 16 + 4 * kg + r) * RS + col] = acc_o[mt][nt][r];
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc_f[mt][nt][r] = acc_o[mt][nt][r] + bv;
             }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc_f[mt][nt][r] = acc_o[mt][nt][r] + bv;
         }
     }
-    lds_barrier();
+    if constexpr (!KVF) lds_barrier();
 
     stamp();
     // ---- phase 5 ----

@@ -67,12 +67,17 @@ struct HeadDev {          // fc1 -> SELU -> K x (fc2 -> SELU -> fc3 -> SELU)
     int k1 = 0;
 };
 
+// CTO_CVT_FOLD, read when a handle is created: "0", unset / "1" / anything else, "q", "kv"
+enum { CVT_FOLD_OFF = 0, CVT_FOLD_DEFAULT = 1, CVT_FOLD_QSIDE = 2, CVT_FOLD_KVSIDE = 3 };
+
 struct BlockDev {
     float *n0g, *n0b, *dwq, *bnq, *wq, *dwkv, *bnkv, *wkv, *wo, *bo, *n1g, *n1b, *w1, *b1, *w2, *b2;
     // the five GEMM weights in fragment order for the fused block kernel (cvt_gemm.h); the row-major ones serve the unfused path
     float *wq_f = nullptr, *wkv_f = nullptr, *wo_f = nullptr, *w1_f = nullptr, *w2_f = nullptr;
     // folded attention weights of a fused stage with C <= 64 (upload_folded), in the fragment order of wq_f / wo_f, or null
     float *mq_f = nullptr, *mo_f = nullptr;
+    // the same matrices as the per-head [2C][C] weight of the k/v-side form's [k'_h | v'_h] GEMM (every fused stage), fragment order, or null
+    float* mkv_f = nullptr;
     // split-operand experiment (CTO_CVT_SPLIT): (hi, lo) 16-bit fragments per GEMM weight, or null
     float *wq_s = nullptr, *wkv_s = nullptr, *wo_s = nullptr, *w1_s = nullptr, *w2_s = nullptr;
 };
@@ -111,7 +116,7 @@ struct cto_model {
     bool fuse_blocks = true;   // fused transformer-block kernel where the stage geometry allows (CTO_CVT_UNFUSED=1 disables)
     bool fuse_embed = true;    // stage embedding + LayerNorm inside the stage's first block (CTO_CVT_NO_EMBED_FUSE=1 disables)
     bool fuse_head = true;     // fc1 + classifier tail inside the network's last block (CTO_CVT_NO_HEAD_FUSE=1 disables)
-    bool fold = true;          // folded attention weights in the fused stages where they are faster (CTO_CVT_FOLD=0 disables)
+    int fold = CVT_FOLD_DEFAULT;   // folded attention weights in the fused stages (CTO_CVT_FOLD: 0 = none, q, kv; else the form that measured fastest)
     // live kernel timing (cto_model_profile)
     bool prof = false;          // the dominant kernel is bracketed by events
     bool prof_all = false;      // ... and BiGRU layer 1 too (cto_model_profile(m, 2))
@@ -317,7 +322,7 @@ struct BlockExtra {            // what the first / last block of the network add
     int n_out = 0;
 };
 
-template <int C, int W, int WKV, int TS, int CIN, bool HEAD, int SPLIT = 0, bool FOLD = false>
+template <int C, int W, int WKV, int TS, int CIN, bool HEAD, int SPLIT = 0, int FOLD = FOLD_NONE>
 int launch_cvt_block(hipStream_t s, float* h, const BlockDev* blocks, int nblk, int heads, int64_t B, const BlockExtra& ex) {
     using G = CvtBlockGeom<C, W, WKV, TS, FOLD, FOLD ? CIN : 0>;
     static_assert(G::LDS_BYTES <= 160 * 1024, "fused CvT block does not fit the 160 KB LDS of a gfx950 CU");
@@ -335,8 +340,11 @@ int launch_cvt_block(hipStream_t s, float* h, const BlockDev* blocks, int nblk, 
     sp.nblk = nblk;
     for (int i = 0; i < nblk; ++i) {
         const BlockDev& b = blocks[i];
-        if (FOLD) CTO_REQUIRE(b.mq_f && b.mo_f, CTO_EINVAL, "folded CvT block without folded weights");
-        sp.blk[i] = CvtBlockParams{b.n0g, b.n0b, b.dwq, b.bnq, FOLD ? b.mq_f : b.wq_f, b.dwkv, b.bnkv, FOLD ? nullptr : b.wkv_f, FOLD ? b.mo_f : b.wo_f, b.bo, b.n1g, b.n1b, b.w1_f, b.b1, b.w2_f, b.b2,
+        if (FOLD == FOLD_Q) CTO_REQUIRE(b.mq_f && b.mo_f, CTO_EINVAL, "folded CvT block without folded weights");
+        if (FOLD == FOLD_KV) CTO_REQUIRE(b.mkv_f, CTO_EINVAL, "folded CvT block without folded weights");
+        // FOLD_Q reads Mq through wq and Mo through wo; FOLD_KV reads [Mq^T | Mo] through wkv and nothing else of the three
+        sp.blk[i] = CvtBlockParams{b.n0g, b.n0b, b.dwq, b.bnq, FOLD == FOLD_Q ? b.mq_f : (FOLD ? nullptr : b.wq_f), b.dwkv, b.bnkv,
+                                   FOLD == FOLD_KV ? b.mkv_f : (FOLD ? nullptr : b.wkv_f), FOLD == FOLD_Q ? b.mo_f : (FOLD ? nullptr : b.wo_f), b.bo, b.n1g, b.n1b, b.w1_f, b.b1, b.w2_f, b.b2,
                                    prof_on ? prof_buf : nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                                    nullptr, nullptr, nullptr, nullptr, nullptr};
         if (SPLIT != 0) {
@@ -372,17 +380,34 @@ int launch_cvt_block(hipStream_t s, float* h, const BlockDev* blocks, int nblk, 
     return CTO_OK;
 }
 
-// Fused geometries that run on folded attention weights unless CTO_CVT_FOLD=0: those that measured faster folded -
-// every one with C <= dim_head = 64, where a folded matrix is no larger than the projection it replaces.
-constexpr bool cvt_fold_geom(int c) { return c <= 64; }
+// The q-side form exists where a folded matrix is no larger than the projection it replaces (C <= dim_head = 64); the k/v-side form in
+// every fused geometry.
+constexpr bool cvt_fold_q_geom(int c) { return c <= 64; }
+// The form a fused geometry runs by default: the one that measured fastest on MI355X (profiles/cvt_kvfold_ab.txt;
+// rocprofv3 averages of 46 launches of the default SNV network, us, unfolded / q-side / k/v-side)
+constexpr int cvt_fold_default(int c) {
+    return c == 128 ? FOLD_KV      // stage 3: 295.6 / -     / 270.7
+         : c == 64  ? FOLD_KV      // stage 2: 125.6 / 107.8 / 94.8
+                    : FOLD_Q;      // stage 1 (C = 16): 42.0 / 23.3 / 23.9 - not faster, stays; C = 32 not timed in this form, stays
+}
+// CTO_CVT_FOLD as the handle holds it -> the form of a stage with C channels
+constexpr int cvt_fold_kind(int mode, int c) {
+    return mode == CVT_FOLD_OFF ? FOLD_NONE : mode == CVT_FOLD_QSIDE ? (cvt_fold_q_geom(c) ? FOLD_Q : FOLD_NONE) : mode == CVT_FOLD_KVSIDE ? FOLD_KV : cvt_fold_default(c);
+}
 
 // The instantiated geometries: (C, W, WKV) -> sites per workgroup and the stage-input channel count whose embedding
 // can run inside the stage's first block.
-template <int C, int W, int WKV, int TS, int CIN, int SPLIT, bool FOLD = false>
+template <int C, int W, int WKV, int TS, int CIN, int SPLIT, int FOLD = FOLD_NONE>
 int dispatch_block_kind(hipStream_t s, float* h, const BlockDev* blocks, int nblk, int heads, int64_t B, const BlockExtra& ex, bool embed, bool head) {
-    if constexpr (FOLD) {
-        return embed ? launch_cvt_block<C, W, WKV, TS, CIN, false, 0, true>(s, h, blocks, nblk, heads, B, ex)
-                     : launch_cvt_block<C, W, WKV, TS, 0, false, 0, true>(s, h, blocks, nblk, heads, B, ex);
+    if constexpr (FOLD != FOLD_NONE) {
+        static_assert(SPLIT == 0, "the folded matrices exist in fp32 only");
+        if constexpr (C == 128 && CvtBlockGeom<C, W, WKV, TS>::HEAD_OK) {      // where the unfolded kernel takes the classifier, this one does
+            static_assert(CvtBlockGeom<C, W, WKV, TS, FOLD, CIN>::HEAD_OK && CvtBlockGeom<C, W, WKV, TS, FOLD, 0>::HEAD_OK, "no room for the classifier tail");
+            if (head) return embed ? launch_cvt_block<C, W, WKV, TS, CIN, true, 0, FOLD>(s, h, blocks, nblk, heads, B, ex)
+                                   : launch_cvt_block<C, W, WKV, TS, 0, true, 0, FOLD>(s, h, blocks, nblk, heads, B, ex);
+        }
+        return embed ? launch_cvt_block<C, W, WKV, TS, CIN, false, 0, FOLD>(s, h, blocks, nblk, heads, B, ex)
+                     : launch_cvt_block<C, W, WKV, TS, 0, false, 0, FOLD>(s, h, blocks, nblk, heads, B, ex);
     }
     if constexpr (C == 128 && CvtBlockGeom<C, W, WKV, TS>::HEAD_OK) {
         if (head) return embed ? launch_cvt_block<C, W, WKV, TS, CIN, true, SPLIT>(s, h, blocks, nblk, heads, B, ex)
@@ -394,14 +419,17 @@ int dispatch_block_kind(hipStream_t s, float* h, const BlockDev* blocks, int nbl
 // split (0 = fp32; 1 = f16, 2 = bf16: experiment) exists for the 64- and 128-channel stages with 16-site tiles
 template <int C, int W, int WKV, int TS, int CIN>
 int dispatch_block(hipStream_t s, float* h, const BlockDev* blocks, int nblk, int heads, int64_t B, const BlockExtra& ex, bool embed, bool head,
-                   int split, bool fold) {
+                   int split, int fold) {
     if constexpr (C % 64 == 0 && MT_EXACT<C, W, WKV, TS>()) {
         if (split == 1) return dispatch_block_kind<C, W, WKV, TS, CIN, 1>(s, h, blocks, nblk, heads, B, ex, embed, head);
         if (split == 2) return dispatch_block_kind<C, W, WKV, TS, CIN, 2>(s, h, blocks, nblk, heads, B, ex, embed, head);
     }
-    if constexpr (cvt_fold_geom(C)) {       // the fp32 kernel on folded attention weights (cvt_block.h: FOLD)
-        if (fold && blocks->mq_f) return dispatch_block_kind<C, W, WKV, TS, CIN, 0, true>(s, h, blocks, nblk, heads, B, ex, embed, head);
+    // the fp32 kernel on folded attention weights (cvt_block.h: FOLD)
+    const int kind = cvt_fold_kind(fold, C);
+    if constexpr (cvt_fold_q_geom(C)) {
+        if (kind == FOLD_Q && blocks->mq_f) return dispatch_block_kind<C, W, WKV, TS, CIN, 0, FOLD_Q>(s, h, blocks, nblk, heads, B, ex, embed, head);
     }
+    if (kind == FOLD_KV && blocks->mkv_f) return dispatch_block_kind<C, W, WKV, TS, CIN, 0, FOLD_KV>(s, h, blocks, nblk, heads, B, ex, embed, head);
     return dispatch_block_kind<C, W, WKV, TS, CIN, 0>(s, h, blocks, nblk, heads, B, ex, embed, head);
 }
 // Sites per workgroup of the stage-1 / stage-2 blocks.  What they trade is LDS per workgroup (q / k / v tiles dominate) against
@@ -429,10 +457,10 @@ bool can_fuse_head(const StageDev& st, const HeadDev& hd) { const FusedGeom* g =
 // nblk consecutive fused transformer blocks of a stage in one launch, when the stage geometry has an instantiation; returns 1 if it
 // ran, 0 if not, < 0 on error
 int try_fused_blocks(hipStream_t s, const StageDev& st, const BlockDev* b, int nblk, float* h, int64_t B, const BlockExtra& ex, bool embed,
-                     bool head, int split, bool fold) {
+                     bool head, int split, int fold) {
     int rc = CTO_OK;
     if (!b->wq_s) split = 0;
-    if (split) fold = false;
+    if (split) fold = CVT_FOLD_OFF;
     if (st.c == 128 && st.w == 5 && st.wkv == 3) rc = dispatch_block<128, 5, 3, CTO_CVT_TS3, 64>(s, h, b, nblk, st.heads, B, ex, embed, head, split, fold);
     else if (st.c == 64 && st.w == 9 && st.wkv == 5) rc = dispatch_block<64, 9, 5, CTO_CVT_TS2, 16>(s, h, b, nblk, st.heads, B, ex, embed, head, split, fold);
     else if (st.c == 16 && st.w == 17 && st.wkv == 9) rc = dispatch_block<16, 17, 9, CTO_CVT_TS1, 34>(s, h, b, nblk, st.heads, B, ex, embed, head, split, fold);
@@ -673,8 +701,12 @@ int upload_split_fragments(const cto_weights* w, const std::string& name, int nt
 // the [64][C] row blocks of to_q / to_kv and Wo_h the [C][64] column block of to_out:
 //   Mq_h = Wq_h^T Wk_h   - stored as the weight [n = h C + c2][k = c1] of the C-wide GEMM  q'_h = yq Mq_h
 //   Mo_h = Wv_h^T Wo_h^T - stored as the weight [n][k = h C + c]       of the GEMM        out += (P_h ykv) Mo_h
-// each formed in double from the fp32 weights and rounded once, then packed like wq_f / wo_f.
-int upload_folded(const cto_weights* w, const std::string& P, int C, int heads, Arena& a, float** mq, float** mo) {
+// each formed in double from the fp32 weights and rounded once, then packed like wq_f / wo_f (mq, mo: null where the q-side form does
+// not exist).  The k/v-side form (FOLD_KV) applies the same rounded matrices to the ykv rows: per head the [2C][C] weight, as [out][in],
+//   rows 0 .. C:   k'_h = ykv Mq_h^T  - [n][k] = Mq_h[n][k]
+//   rows C .. 2C:  v'_h = ykv Mo_h    - [n][k] = Mo_h[k][n]
+// the transpose of how the two are laid out for the q side, packed as a (heads * 2C)-row weight with k extent C.
+int upload_folded(const cto_weights* w, const std::string& P, int C, int heads, Arena& a, float** mq, float** mo, float** mkv) {
     int rc = CTO_OK;
     const int inner = 64 * heads;
     GETW(wq, P + ".0.fn.to_q.net.2.weight", int64_t(inner) * C);
@@ -682,7 +714,7 @@ int upload_folded(const cto_weights* w, const std::string& P, int C, int heads, 
     GETW(wo, P + ".0.fn.to_out.0.weight", int64_t(C) * inner);
     const float* wk = wkv->data();
     const float* wv = wkv->data() + size_t(inner) * C;
-    std::vector<float> q(size_t(heads) * C * C), o(size_t(C) * heads * C);
+    std::vector<float> q(size_t(heads) * C * C), o(size_t(C) * heads * C), kv(size_t(heads) * 2 * C * C);
     for (int hh = 0; hh < heads; ++hh)
         for (int x = 0; x < C; ++x)
             for (int y = 0; y < C; ++y) {
@@ -694,9 +726,12 @@ int upload_folded(const cto_weights* w, const std::string& P, int C, int heads, 
                 }
                 q[(size_t(hh) * C + x) * C + y] = float(sq);
                 o[size_t(x) * heads * C + size_t(hh) * C + y] = float(so);
+                kv[(size_t(hh) * 2 * C + y) * C + x] = float(sq);
+                kv[(size_t(hh) * 2 * C + C + x) * C + y] = float(so);
             }
-    if ((rc = a.upload(pack_fragments(q.data(), heads * C / 16, C / 16), mq)) != CTO_OK) return rc;
-    return a.upload(pack_fragments(o.data(), C / 16, heads * C / 16), mo);
+    if (mq && (rc = a.upload(pack_fragments(q.data(), heads * C / 16, C / 16), mq)) != CTO_OK) return rc;
+    if (mo && (rc = a.upload(pack_fragments(o.data(), C / 16, heads * C / 16), mo)) != CTO_OK) return rc;
+    return a.upload(pack_fragments(kv.data(), heads * 2 * C / 16, C / 16), mkv);
 }
 int upload_fragments(const cto_weights* w, const std::string& name, int ntiles, int kch, Arena& a, float** out) {
     int rc = CTO_OK;
@@ -857,7 +892,8 @@ extern "C" int cto_cvt_create_ex(const cto_weights* w, const cto_cvt_cfg* cfg, i
                 (rc = upload_fragments(w, P + ".1.fn.net.0.weight", 4 * NC16, NC16, a, &b.w1_f)) ||
                  (rc = upload_fragments(w, P + ".1.fn.net.3.weight", NC16, 4 * NC16, a, &b.w2_f))))
                 return fail(rc);
-            if (fused_geom(st) && cvt_fold_geom(C) && (rc = upload_folded(w, P, C, st.heads, a, &b.mq_f, &b.mo_f))) return fail(rc);
+            if (fused_geom(st) && (rc = upload_folded(w, P, C, st.heads, a, cvt_fold_q_geom(C) ? &b.mq_f : nullptr, cvt_fold_q_geom(C) ? &b.mo_f : nullptr, &b.mkv_f)))
+                return fail(rc);
             if (m->cvt_split && C % 64 == 0) {
                 const bool f16 = m->cvt_split == 1;
                 if ((rc = upload_split_fragments(w, P + ".0.fn.to_q.net.2.weight", NI, C / 32, f16, a, &b.wq_s)) ||
@@ -902,7 +938,11 @@ extern "C" int cto_cvt_create_ex(const cto_weights* w, const cto_cvt_cfg* cfg, i
     if (const char* e = getenv("CTO_CVT_UNFUSED")) m->fuse_blocks = !(e[0] == '1');
     if (const char* e = getenv("CTO_CVT_NO_EMBED_FUSE")) m->fuse_embed = !(e[0] == '1');
     if (const char* e = getenv("CTO_CVT_NO_HEAD_FUSE")) m->fuse_head = !(e[0] == '1');
-    if (const char* e = getenv("CTO_CVT_FOLD")) m->fold = !(e[0] == '0');
+    if (const char* e = getenv("CTO_CVT_FOLD")) {
+        const std::string v(e);
+        // off is a leading '0', as it always was; the two forms are matched whole; anything else is the default
+        m->fold = e[0] == '0' ? CVT_FOLD_OFF : v == "q" ? CVT_FOLD_QSIDE : v == "kv" ? CVT_FOLD_KVSIDE : CVT_FOLD_DEFAULT;
+    }
     *out = m.release();
     return CTO_OK;
 }
