@@ -10,6 +10,8 @@ germline-looking PASS calls to LowQual and append the Verdict_* tags.  cna_germl
 starts it: the seven steps, in this process.  cal_af_distribution is the reference's src/cal_af_distribution.py, the AF half of its
 compare_vcf step: per truth variant the depth, ALT count and haplotype counts the tumour BAM shows, one pass over the BAM.  compare_vcf is the command the reference's quick demos end with (src/compare_vcf.py): the
 calls against a truth set -> precision, recall and F1, the classification and the cut-off sweeps on the GPU.
+select_hetero_snp_for_phasing and phase_tumor are the long-read steps between STEP 3 and STEP 4 of run_clairs_to: the heterozygous SNP
+calls of a contig, then their phase and the haplotagged BAM (HP, PS) that haplotype_filtering reads - instead of longphase / whatshap.
     usage: python -m clairs_to_amd compare_vcf --truth_vcf_fn TRUTH --input_vcf_fn CALLS [--bed_fn BED] [--ctg_name CTG] [--output_dir DIR]"""
 import importlib
 import sys
@@ -17,7 +19,8 @@ import sys
 SUBMODULES = ("extract_candidates_calling", "concat_files", "create_tensor_pileup_calling", "predict", "call_variants", "pileup_call", "call_chunks",
               "sort_vcf", "postprocess_vcf", "haplotype_filtering", "realign_reads", "realign_variants",
               "nonsomatic_tagging", "postfilter_variants", "allele_counter", "get_logr_and_baf", "predict_germline_genotypes", "aspcf", "run_ascat",
-              "correct_logr", "tag_germline_variant", "cna_germline_tagging", "cal_af_distribution", "compare_vcf")
+              "correct_logr", "tag_germline_variant", "cna_germline_tagging", "cal_af_distribution", "compare_vcf",
+              "select_hetero_snp_for_phasing", "phase_tumor")
 
 
 def dispatch(name, argv):

@@ -90,6 +90,16 @@ class AfStats(C.Structure):
                 ("host_loci", c_i64), ("ms_inflate", C.c_double), ("ms_records", C.c_double), ("ms_count", C.c_double)]
 
 
+class PhaseStats(C.Structure):
+    _fields_ = [("n_chunks", c_i64), ("n_reads_entered", c_i64), ("n_blocks", c_i64), ("inflated_bytes", c_i64), ("fallback_chunks", c_i64),
+                ("host_loci", c_i64), ("ms_inflate", C.c_double), ("ms_records", C.c_double), ("ms_count", C.c_double),
+                ("n_phase_blocks", c_i64), ("n_merged_reads", c_i64), ("ms_copy", C.c_double), ("ms_phase", C.c_double)]
+
+
+class PhaseResult(C.Structure):
+    _fields_ = [("n_reads", c_i64), ("n_obs", c_i64), ("voff", c_vp), ("obs_off", c_vp), ("obs", c_vp), ("hp", c_vp), ("ps", c_vp)]
+
+
 class HapRec(C.Structure):
     _fields_ = [("read", c_i32), ("indel_off", c_i32), ("indel_len", c_i32), ("joined", c_i32), ("bq", c_i32), ("mq", c_i32),
                 ("base", C.c_uint8), ("hp", C.c_uint8), ("hp_single", C.c_uint8), ("pad_", C.c_uint8)]
@@ -256,6 +266,9 @@ SYMBOLS = {
                                     c_vp, C.POINTER(AlleleStats)]),
     "cto_af_tallies": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_int, C.c_int,
                                  C.c_int, C.c_int, c_vp, c_vp, C.POINTER(AfStats)]),
+    "cto_phase_reads": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, c_vp, c_vp, c_vp, c_i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_vp,
+                                  c_vp, c_vp, c_vp, C.POINTER(C.POINTER(PhaseResult)), C.POINTER(PhaseStats)]),
+    "cto_phase_result_free": (None, [C.POINTER(PhaseResult)]),
     "cto_germline_window_dist": (C.c_int, [c_vp, c_vp, c_i64, C.c_int, C.c_int, c_vp, C.POINTER(GermlineStats)]),
     "cto_aspcf_windows": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, C.c_int, C.c_double, C.c_int, c_vp, c_vp, C.POINTER(AspcfStats)]),
     "cto_aspcf_squares": (C.c_int, [c_vp, c_i64, c_vp]),

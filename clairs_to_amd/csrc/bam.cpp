@@ -707,6 +707,124 @@ int af_tallies_host_range(const char* bam_path, const char* bai_path, const char
     return CTO_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ read phasing, host path
+// The plain definition of the phasing rules (listed in full at the top of csrc/phase.hip, which holds the C entry point and the device
+// path that is held equal to this one): observations per chunk of sites, their merge by virtual offset, the link table, the sequential
+// phase pass (which both paths run here) and the reads' haplotypes.
+
+// The observations of the sites [a, b) by every read that enters their stretch [pos[a] - 1, pos[b] - 1) - the stretches of a call's
+// chunks tile pos[0] - 1 .. pos[n - 1], so a read enters at least one chunk exactly when it enters the whole.
+int phase_observe_host_range(const char* bam_path, const char* bai_path, const char* ctg_name, const PhaseSites& S, int64_t a, int64_t b,
+                             const PhaseParams& pr, PhaseReads* out, double* ms) {
+    const double t0 = now();
+    out->voff.clear(); out->obs.clear(); out->off.assign(1, 0);
+    const int64_t beg0 = int64_t(S.pos[a]) - 1, end0 = b < S.n ? int64_t(S.pos[b]) - 1 : int64_t(S.pos[S.n - 1]);
+    BamRegion rg;
+    CTO_REQUIRE(rg.open("cto_phase_reads", bam_path, bai_path, ctg_name, beg0, end0, false, false), CTO_EINVAL, "%s", rg.err.c_str());
+    const int32_t *p0 = S.pos + a, *p1 = S.pos + b;
+    for (BamRecord r;;) {
+        const int got = rg.next(&r);
+        CTO_REQUIRE(got >= 0, CTO_EINVAL, "%s", rg.err.c_str());
+        if (got == 0) break;
+        const int flag = r.flag;
+        if ((flag & pr.excl_flags) || (flag & 4) || r.mapq < pr.min_mq || r.n_cig == 0 || r.l_seq <= 0 || r.pos < 0) continue;
+        if ((flag & 1) && !(flag & 2)) continue;
+        CTO_REQUIRE(rg.lay_out(&r), CTO_EINVAL, "%s", rg.err.c_str());
+        const int enters = rg.enters(r);
+        CTO_REQUIRE(enters >= 0, CTO_EINVAL, "%s", rg.err.c_str());
+        if (!enters) continue;
+        out->voff.push_back(rg.rec_voff);
+        int64_t li = a + (std::lower_bound(p0, p1, r.pos + 1) - p0);
+        int32_t rp = r.pos, qp = 0;
+        for (int k = 0; k < r.n_ops && li < b; ++k) {
+            const int len = int(r.op(k) >> 4), opc = int(r.op(k) & 15);
+            if (consumes_ref(opc)) {
+                for (; li < b && int64_t(S.pos[li]) - 1 < int64_t(rp) + len; ++li) {
+                    if (opc != 0 && opc != 7 && opc != 8) continue;                 // D, N: nothing
+                    const int q = qp + (S.pos[li] - 1 - rp);
+                    const int c = (r.sq[q >> 1] >> ((~q & 1) << 2)) & 15;
+                    if (c != 1 && c != 2 && c != 4 && c != 8) continue;             // N, IUPAC codes, `=`: nothing
+                    if (c == phase_base_code(S.ref[li])) out->obs.push_back(int32_t(li * 2));
+                    else if (c == phase_base_code(S.alt[li])) out->obs.push_back(int32_t(li * 2 + 1));
+                }
+                rp += len;
+            }
+            if (consumes_query(opc)) qp += len;
+        }
+        out->off.push_back(int64_t(out->obs.size()));
+    }
+    if (ms) *ms = now() - t0;
+    return CTO_OK;
+}
+
+// The chunks' reads as one list in file order: a read that entered several chunks is one read, its observations in site order
+// (chunks ascend, and each site belongs to one chunk)
+void phase_merge(const std::vector<PhaseReads>& parts, PhaseReads* out, int64_t* n_merged) {
+    struct Key { uint64_t voff; uint32_t part, idx; };
+    std::vector<Key> keys;
+    for (size_t p = 0; p < parts.size(); ++p)
+        for (size_t i = 0; i < parts[p].voff.size(); ++i) keys.push_back(Key{parts[p].voff[i], uint32_t(p), uint32_t(i)});
+    std::stable_sort(keys.begin(), keys.end(), [](const Key& x, const Key& y) { return x.voff < y.voff; });
+    out->voff.clear(); out->obs.clear(); out->off.assign(1, 0);
+    int64_t merged = 0;
+    for (size_t k = 0; k < keys.size(); ++k) {
+        const bool first = k == 0 || keys[k].voff != keys[k - 1].voff;
+        if (first) out->voff.push_back(keys[k].voff);
+        else if (k < 2 || keys[k - 2].voff != keys[k].voff) ++merged;
+        const PhaseReads& P = parts[keys[k].part];
+        out->obs.insert(out->obs.end(), P.obs.begin() + P.off[keys[k].idx], P.obs.begin() + P.off[keys[k].idx + 1]);
+        if (first) out->off.push_back(0);
+        out->off.back() = int64_t(out->obs.size());
+    }
+    if (n_merged) *n_merged = merged;
+}
+
+void phase_link_host(const PhaseReads& R, int64_t n, int K, int32_t* link) {
+    std::fill(link, link + n * K * 2, 0);
+    for (size_t r = 0; r + 1 < R.off.size(); ++r)
+        for (int64_t i = R.off[r]; i < R.off[r + 1]; ++i)
+            for (int64_t j = i + 1; j < R.off[r + 1] && (R.obs[j] >> 1) - (R.obs[i] >> 1) <= K; ++j)
+                ++link[((int64_t(R.obs[i] >> 1)) * K + ((R.obs[j] >> 1) - (R.obs[i] >> 1) - 1)) * 2 + ((R.obs[i] ^ R.obs[j]) & 1)];
+}
+
+// The phase pass: one scan over the sites, each judged by the link counts to the phased sites of the open block within K in front of it
+void phase_sites(const int32_t* link, const int32_t* pos, int64_t n, int K, int8_t* phase, int32_t* ps, int32_t* block, int64_t* n_blocks) {
+    int32_t cur = -1, cur_ps = 0;
+    for (int64_t b = 0; b < n; ++b) {
+        int64_t same = 0, flip = 0;
+        for (int64_t a = std::max<int64_t>(0, b - K); a < b && cur >= 0; ++a) {
+            if (block[a] != cur) continue;
+            const int32_t* l = link + (a * K + (b - a - 1)) * 2;
+            same += l[phase[a]];
+            flip += l[1 - phase[a]];
+        }
+        const int64_t T = same + flip;
+        if (b == 0 || T < 2) { ++cur; cur_ps = pos[b]; phase[b] = 0; }
+        else if (4 * std::min(same, flip) > T) { phase[b] = -1; ps[b] = 0; block[b] = -1; continue; }
+        else phase[b] = flip > same;
+        block[b] = cur;
+        ps[b] = cur_ps;
+    }
+    if (n_blocks) *n_blocks = cur + 1;
+}
+
+void phase_assign_host(const PhaseReads& R, const int8_t* phase, const int32_t* block, const int32_t* ps, uint8_t* hp, int32_t* rps) {
+    for (size_t r = 0; r + 1 < R.off.size(); ++r) {
+        int best_h1 = 0, best_h2 = 0, best_ps = 0, h1 = 0, h2 = 0, cur = -1, cur_ps = 0;
+        auto close = [&] { if (h1 + h2 > best_h1 + best_h2) { best_h1 = h1; best_h2 = h2; best_ps = cur_ps; } };
+        for (int64_t i = R.off[r]; i < R.off[r + 1]; ++i) {
+            const int s = R.obs[i] >> 1;
+            if (phase[s] < 0) continue;
+            if (block[s] != cur) { close(); cur = block[s]; cur_ps = ps[s]; h1 = h2 = 0; }
+            if (((R.obs[i] & 1) ^ phase[s]) == 0) ++h1; else ++h2;
+        }
+        close();
+        const int t = best_h1 + best_h2;
+        hp[r] = t > 0 && 10 * best_h1 >= 6 * t ? 1 : (t > 0 && 10 * best_h2 >= 6 * t ? 2 : 0);
+        rps[r] = hp[r] ? best_ps : 0;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ haplotype windows, host path
 // The plain definition of the rules by which a haplotype-filter job is built from the BAM (listed in full at the top of
 // csrc/hapwindows.hip, which holds the C entry point and the device path that is held equal to this one): one pass in file order over

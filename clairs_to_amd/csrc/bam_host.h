@@ -209,6 +209,13 @@ struct Bgzf {
         if (block_coffset >= 0 && upos >= blen) return uint64_t(next_coffset) << 16;
         return (uint64_t(block_coffset) << 16) | uint64_t(upos);
     }
+    // tell() once the block that holds the next byte is loaded: the one name of a record's place that does not depend on how the
+    // reader came there (the device derives the same from its block table); at the end of the file, or where the next block does
+    // not load, it is tell() and read() reports what is wrong
+    uint64_t settle() {
+        while (block_coffset >= 0 && upos >= blen && load(next_coffset)) {}
+        return tell();
+    }
     // reads exactly n bytes across block boundaries; false at EOF / error
     bool read(void* dst, size_t n) {
         uint8_t* d = static_cast<uint8_t*>(dst);
@@ -410,6 +417,7 @@ struct BamRegion {
     std::vector<uint64_t> linear;        // the contig's linear index, when asked for
     int64_t beg0 = 0, end0 = 0;
     std::vector<uint8_t> rec;            // the record next() read last; a consumer that keeps a record swaps it out
+    uint64_t rec_voff = 0;               // its virtual offset (of its block_size field)
     size_t ci = 0;                       // chunk being read
     bool in_chunk = false;
 
@@ -468,6 +476,7 @@ struct BamRegion {
             }
             if (bz.tell() >= chunks[ci].end) { ++ci; in_chunk = false; continue; }
             uint8_t h4[4];
+            rec_voff = bz.settle();
             if (!bz.read(h4, 4)) {
                 if (!bz.err.empty()) { fail("%s", bz.err.c_str()); return -1; }
                 break;                                                          // clean end of the file

@@ -153,4 +153,19 @@ struct AfLoci { const int32_t* pos; const uint8_t *kind, *base; const int32_t* d
 struct AfParams { int min_mq, excl_flags, max_depth, with_hp; };
 int af_tallies_host_range(const char* bam_path, const char* bai_path, const char* ctg_name, const AfLoci& loci, const int64_t* sel, int64_t n_sel,
                           const AfParams& pr, int32_t* out, int64_t* n_entered, double* ms_records, double* ms_count);
+// Read phasing (the C entry point, the rules and the device path: csrc/phase.hip; the host rules and the phase pass: csrc/bam.cpp).
+// pos: 1-based, strictly ascending; ref / alt: one ASCII letter per site.  A read list is a CSR: reads in file order, named by the
+// virtual offset of their record, each with its observations site * 2 + allele in ascending site order.
+struct PhaseSites { const int32_t* pos; const uint8_t *ref, *alt; int64_t n; };
+struct PhaseParams { int min_mq, excl_flags, link_span; };
+struct PhaseReads { std::vector<uint64_t> voff; std::vector<int64_t> off{0}; std::vector<int32_t> obs; };
+inline int phase_base_code(uint8_t letter) {             // the 4-bit code of a BAM sequence for A C G T (either case), 0 for anything else
+    switch (letter & 0xdf) { case 'A': return 1; case 'C': return 2; case 'G': return 4; case 'T': return 8; default: return 0; }
+}
+int phase_observe_host_range(const char* bam_path, const char* bai_path, const char* ctg_name, const PhaseSites& S, int64_t a, int64_t b,
+                             const PhaseParams& pr, PhaseReads* out, double* ms);
+void phase_merge(const std::vector<PhaseReads>& parts, PhaseReads* out, int64_t* n_merged);
+void phase_link_host(const PhaseReads& R, int64_t n, int K, int32_t* link);          // link: n x K x 2, zeroed by the call
+void phase_sites(const int32_t* link, const int32_t* pos, int64_t n, int K, int8_t* phase, int32_t* ps, int32_t* block, int64_t* n_blocks);
+void phase_assign_host(const PhaseReads& R, const int8_t* phase, const int32_t* block, const int32_t* ps, uint8_t* hp, int32_t* rps);
 }  // namespace cto

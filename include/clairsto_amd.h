@@ -865,6 +865,59 @@ int cto_af_tallies(const char* bam_path, const char* bai_path, const char* ctg_n
                    int32_t* out /* n_loci x 8: depth, alt, h0 h1 h2, a0 a1 a2; host */, cto_af_stats* stats);
 
 /* ----------------------------------------------------------------------------------------------
+ * Read phasing (csrc/phase.hip, host rules in csrc/bam.cpp): heterozygous SNP sites of one contig -> their phase and phase set, and
+ * per read the haplotype it is tagged with - what `longphase phase` + `longphase haplotag` (or whatshap) do between STEP 3 and STEP 4
+ * of run_clairs_to.  PARITY UNPINNED against longphase and whatshap (neither exists on the build or GPU machines): the rules below,
+ * listed in full at the top of csrc/phase.hip, are the definition.  All arithmetic is integer; the device path returns the host
+ * path's result exactly.
+ *   pos/ref/alt  n sites: 1-based positions on ctg_name, strictly ascending; one ASCII letter each (either case; a letter that is not
+ *                A C G T matches no base)
+ *   reads        enter as in cto_af_tallies (unmapped, excl_flags, MAPQ < min_mq, orphans, no CIGAR / SEQ) when they overlap
+ *                pos[0] .. pos[n - 1]; a read is named by the virtual offset of its record
+ *   observations at a site inside the read's span an M / = / X base equal to REF observes allele 0, equal to ALT allele 1; another
+ *                letter, N, an IUPAC code, a deletion or a reference skip observes nothing; an insertion behind the base changes nothing
+ *   link         int32 n x link_span x 2, on the host: over every read and every pair of its observations at sites a < b with
+ *                b - a <= link_span (in site index), link[a][b - a - 1][allele_a != allele_b] += 1
+ *   phase, ps    site 0 opens block 0 with phase 0; site b sums over the phased sites a in [b - link_span, b - 1] of the open block
+ *                same (link[a][..][0] when phase[a] == 0, else [1]) and flip (the other), T = same + flip: T < 2 opens a new block
+ *                with phase 0; else 4 * min(same, flip) > T leaves b unphased (phase -1, ps 0: no votes later, no block); else
+ *                phase[b] = flip > same in the open block.  ps = position of the block's first site.
+ *   read hp/ps   an observation at a phased site votes for haplotype 1 + (allele ^ phase) in that site's block; the read takes the block
+ *                with the most votes (ties: the lowest); with h1, h2 its votes there hp = 1 when 10 h1 >= 6 (h1 + h2), 2 when
+ *                10 h2 >= 6 (h1 + h2), else 0 (untagged, ps 0)
+ *   where       0: host (`host_threads` threads over chunks of sites; 0 = one per core, at most 32); 1: device - per chunk the allele
+ *               counter's front end, one wave per entered read for the observations; the chunks' reads are merged by virtual offset on
+ *               the host; link counts and read assignment are kernels over the merged reads, the phase pass between them is host code.
+ *               A damaged chunk is redone by the host path (fallback_chunks).
+ *   result      *out receives the reads (file order); free it with cto_phase_result_free
+ *   stats       may be NULL.  n_reads_entered counts a read once per chunk it enters; n_merged_reads those that entered several;
+ *               ms_inflate = copy up + inflate, ms_records = CRC .. entered reads, ms_count = the observation, link and assignment
+ *               kernels, ms_copy = the copies down and the merged reads' copy up (HIP events; the host path reports its wall times
+ *               in ms_records / ms_count), ms_phase = the phase pass (host wall time); host_loci stays 0 (the field keeps the shape of
+ *               cto_af_stats: no site is redone singly here)
+ * CTO_PHASE_CHUNK_BYTES (environment, for tests): the budget of inflated bytes per chunk, as CTO_AF_CHUNK_BYTES.
+ * ---------------------------------------------------------------------------------------------- */
+#define CTO_PHASE_MAX_LINK_SPAN 64
+typedef struct cto_phase_stats { int64_t n_chunks, n_reads_entered, n_blocks, inflated_bytes, fallback_chunks, host_loci;
+                                 double ms_inflate, ms_records, ms_count;
+                                 int64_t n_phase_blocks, n_merged_reads; double ms_copy, ms_phase; } cto_phase_stats;
+typedef struct cto_phase_result {
+    int64_t n_reads, n_obs;
+    uint64_t* voff;          /* n_reads: virtual offset of the record                   */
+    int64_t* obs_off;        /* n_reads + 1                                             */
+    int32_t* obs;            /* n_obs: site index * 2 + allele, ascending per read      */
+    uint8_t* hp;             /* n_reads: 0 untagged, 1, 2                               */
+    int32_t* ps;             /* n_reads: the phase set of the tag, 0 when untagged      */
+} cto_phase_result;
+int cto_phase_reads(const char* bam_path, const char* bai_path, const char* ctg_name,
+                    const int32_t* pos /* 1-based, strictly ascending */, const uint8_t* ref, const uint8_t* alt, int64_t n,
+                    int min_mq, int excl_flags, int link_span,
+                    int where /* 0 host, 1 device */, int host_threads, void* stream,
+                    int8_t* phase /* n */, int32_t* ps /* n */, int32_t* link /* n x link_span x 2, may be NULL */,
+                    cto_phase_result** out, cto_phase_stats* stats);
+void cto_phase_result_free(cto_phase_result* r);
+
+/* ----------------------------------------------------------------------------------------------
  * Germline genotypes (csrc/germline.hip): the window distances of the reference's predictGermlineGenotypes
  * (src/verdict/predict_germline_genotypes.py:70-154, step 4 of the Verdict chain), over runs of undecided probes.
  *   c               the mirrored BAFs min(baf, 1 - baf) of the undecided probes, run after run, fp64 on the host; no NaN
