@@ -12,6 +12,8 @@ compare_vcf step: per truth variant the depth, ALT count and haplotype counts th
 calls against a truth set -> precision, recall and F1, the classification and the cut-off sweeps on the GPU.
 select_hetero_snp_for_phasing and phase_tumor are the long-read steps between STEP 3 and STEP 4 of run_clairs_to: the heterozygous SNP
 calls of a contig, then their phase and the haplotagged BAM (HP, PS) that haplotype_filtering reads - instead of longphase / whatshap.
+gen_contaminated_bam is the reference's src/gen_contaminated_bam.py: a tumour BAM of a chosen purity from a tumour and a normal BAM -
+coverage, subsample and merge on the GPU instead of mosdepth and samtools.
     usage: python -m clairs_to_amd compare_vcf --truth_vcf_fn TRUTH --input_vcf_fn CALLS [--bed_fn BED] [--ctg_name CTG] [--output_dir DIR]"""
 import importlib
 import sys
@@ -20,7 +22,7 @@ SUBMODULES = ("extract_candidates_calling", "concat_files", "create_tensor_pileu
               "sort_vcf", "postprocess_vcf", "haplotype_filtering", "realign_reads", "realign_variants",
               "nonsomatic_tagging", "postfilter_variants", "allele_counter", "get_logr_and_baf", "predict_germline_genotypes", "aspcf", "run_ascat",
               "correct_logr", "tag_germline_variant", "cna_germline_tagging", "cal_af_distribution", "compare_vcf",
-              "select_hetero_snp_for_phasing", "phase_tumor")
+              "select_hetero_snp_for_phasing", "phase_tumor", "gen_contaminated_bam")
 
 
 def dispatch(name, argv):

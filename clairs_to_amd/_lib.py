@@ -100,6 +100,16 @@ class PhaseResult(C.Structure):
     _fields_ = [("n_reads", c_i64), ("n_obs", c_i64), ("voff", c_vp), ("obs_off", c_vp), ("obs", c_vp), ("hp", c_vp), ("ps", c_vp)]
 
 
+class ContamStats(C.Structure):
+    _fields_ = [("n_chunks", c_i64), ("n_blocks", c_i64), ("inflated_bytes", c_i64), ("fallback_chunks", c_i64), ("n_records", c_i64),
+                ("candidates", c_i64 * 2), ("kept", c_i64 * 2), ("out_bytes", c_i64), ("out_blocks", c_i64),
+                ("ms_inflate", C.c_double), ("ms_kernels", C.c_double), ("ms_copy", C.c_double), ("ms_write", C.c_double)]
+
+
+class CovRow(C.Structure):
+    _fields_ = [("length", c_i64), ("bases", c_i64), ("tid", c_i32), ("min", c_i32), ("max", c_i32), ("pad_", c_i32)]
+
+
 class HapRec(C.Structure):
     _fields_ = [("read", c_i32), ("indel_off", c_i32), ("indel_len", c_i32), ("joined", c_i32), ("bq", c_i32), ("mq", c_i32),
                 ("base", C.c_uint8), ("hp", C.c_uint8), ("hp_single", C.c_uint8), ("pad_", C.c_uint8)]
@@ -269,6 +279,10 @@ SYMBOLS = {
     "cto_phase_reads": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, c_vp, c_vp, c_vp, c_i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_vp,
                                   c_vp, c_vp, c_vp, C.POINTER(C.POINTER(PhaseResult)), C.POINTER(PhaseStats)]),
     "cto_phase_result_free": (None, [C.POINTER(PhaseResult)]),
+    "cto_bam_coverage": (c_i64, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, c_vp, C.POINTER(CovRow), c_i64, C.POINTER(ContamStats)]),
+    "cto_bam_mix": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_uint32, C.c_char_p, C.c_int, C.c_int,
+                              c_vp, C.POINTER(ContamStats)]),
+    "cto_subsample_keys": (C.c_int, [c_vp, c_vp, c_i64, C.c_uint32, C.c_int, c_vp, c_vp]),
     "cto_germline_window_dist": (C.c_int, [c_vp, c_vp, c_i64, C.c_int, C.c_int, c_vp, C.POINTER(GermlineStats)]),
     "cto_aspcf_windows": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, C.c_int, C.c_double, C.c_int, c_vp, c_vp, C.POINTER(AspcfStats)]),
     "cto_aspcf_squares": (C.c_int, [c_vp, c_i64, c_vp]),

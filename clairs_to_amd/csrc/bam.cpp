@@ -37,8 +37,10 @@
 // device, csrc/inflate.hip) are looked up by file offset and CRC-checked the same way.  Columns are built in runs of requested
 // positions, read by read (Producer below).
 // The formats themselves - BGZF, the index, the grammar of an alignment record - are read by csrc/bam_host.h; what is here are its consumers.
+#include <atomic>
 #include <chrono>
 #include <deque>
+#include <map>
 #include <memory>
 #include <thread>
 #include <unordered_map>
@@ -966,6 +968,305 @@ int hap_windows_host(const char* bam_path, const char* bai_path, const char* ctg
             raw->rse_off.push_back(int64_t(raw->rse.size()));
         }
     if (n_entered) *n_entered = entered;
+    return CTO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ coverage, subsample and merge, host path
+// The plain definition of the rules listed at the top of csrc/contam.hip (which holds the C entry points and the device path that is
+// held equal to this one), window by window, and the writer of the output BAM and its index.
+
+int contam_read_header(const char* who, const char* bam_path, BamHeader* out) {
+    Bgzf bz;
+    CTO_REQUIRE(bz.open(bam_path), CTO_EINVAL, "%s: %s", who, bz.err.c_str());
+    std::vector<uint8_t>& raw = out->raw;
+    raw.assign(8, 0);
+    CTO_REQUIRE(bz.read(raw.data(), 8) && memcmp(raw.data(), "BAM\1", 4) == 0, CTO_EINVAL, "%s: %s is not a BAM file%s%s", who, bam_path,
+                bz.err.empty() ? "" : ": ", bz.err.c_str());
+    const int l_text = le32(raw.data() + 4);
+    CTO_REQUIRE(l_text >= 0 && l_text <= (1 << 28), CTO_EINVAL, "%s: %s: bad header text length", who, bam_path);
+    raw.resize(size_t(8) + size_t(l_text) + 4);
+    CTO_REQUIRE(bz.read(raw.data() + 8, size_t(l_text) + 4), CTO_EINVAL, "%s: %s: truncated header", who, bam_path);
+    const int n_ref = le32(raw.data() + 8 + size_t(l_text));
+    CTO_REQUIRE(n_ref >= 0, CTO_EINVAL, "%s: %s: bad reference count", who, bam_path);
+    for (int r = 0; r < n_ref; ++r) {
+        uint8_t h4[4];
+        CTO_REQUIRE(bz.read(h4, 4) && le32(h4) > 0 && le32(h4) <= 65536, CTO_EINVAL, "%s: %s: bad reference list", who, bam_path);
+        const size_t l_name = size_t(le32(h4)), at = raw.size();
+        raw.resize(at + 4 + l_name + 4);
+        memcpy(raw.data() + at, h4, 4);
+        CTO_REQUIRE(bz.read(raw.data() + at + 4, l_name + 4), CTO_EINVAL, "%s: %s: truncated reference list", who, bam_path);
+        const char* nm = reinterpret_cast<const char*>(raw.data() + at + 4);
+        out->names.emplace_back(nm, strnlen(nm, l_name));
+        out->lens.push_back(int64_t(le32(raw.data() + at + 4 + l_name)));
+    }
+    return CTO_OK;
+}
+
+int contam_plan_windows(const char* who, const char* const* bams, const char* const* bais, int n_src, const char* ctg_name, int64_t L,
+                        int64_t budget, std::vector<int64_t>* cuts) {
+    const int64_t nw = (L + kContamWindow - 1) / kContamWindow;
+    cuts->assign(1, 0);
+    if (nw == 0) return CTO_OK;
+    std::vector<int64_t> bytes(size_t(nw) + 1, 0);                   // compressed bytes of all sources in front of window w
+    for (int s = 0; s < n_src; ++s) {
+        BamRegion rg;
+        CTO_REQUIRE(rg.open(who, bams[s], bais[s], ctg_name, 0, L, true, false), CTO_EINVAL, "%s", rg.err.c_str());
+        if (rg.chunks.empty() || rg.linear.empty()) continue;
+        int64_t file_lo = int64_t(rg.chunks.front().beg >> 16), file_hi = 0;
+        for (const Chunk& c : rg.chunks) file_hi = std::max<int64_t>(file_hi, int64_t(c.end >> 16) + 65536);
+        int64_t prev = file_lo;
+        for (int64_t w = 0; w <= nw; ++w) {
+            int64_t v = file_hi;
+            if (w < int64_t(rg.linear.size())) {
+                v = int64_t(rg.linear[size_t(w)] >> 16);
+                if (v == 0) v = prev;                                // a window without alignments
+                v = std::max(std::min(std::max(v, file_lo), file_hi), prev);
+            }
+            bytes[size_t(w)] += v - file_lo;
+            prev = v;
+        }
+    }
+    int64_t a = 0;
+    for (int64_t w = 1; w < nw; ++w)
+        if (4 * (bytes[size_t(w) + 1] - bytes[size_t(a)]) + (w + 1 - a) > budget || w + 1 - a > kContamMaxWindows) { cuts->push_back(w); a = w; }
+    cuts->push_back(nw);
+    return CTO_OK;
+}
+
+int cov_window_host(const char* bam_path, const char* bai_path, const char* ctg_name, int64_t w0, int64_t w1, int64_t L, std::vector<int32_t>* carry,
+                    int64_t* bases, int32_t* mn, int32_t* mx, int64_t* n_counted) {
+    const int64_t e1 = std::min(w1, L), n = e1 - w0;                 // the window's positions inside the contig: [w0, e1)
+    std::vector<int32_t> diff(size_t(n) + 1, 0), open;
+    int64_t b = 0, counted = 0;
+    int32_t depth = int32_t(carry->size());
+    for (int32_t e : *carry) {
+        if (e < e1) --diff[size_t(e - w0)];
+        b += std::min<int64_t>(e, e1) - w0;
+        if (e > e1) open.push_back(e);
+    }
+    BamRegion rg;
+    CTO_REQUIRE(rg.open("cto_bam_coverage", bam_path, bai_path, ctg_name, w0, e1, false, false), CTO_EINVAL, "%s", rg.err.c_str());
+    for (BamRecord r;;) {
+        const int got = rg.next(&r);
+        CTO_REQUIRE(got >= 0, CTO_EINVAL, "%s", rg.err.c_str());
+        if (got == 0) break;
+        if (r.pos < w0 || (r.flag & kCovExclFlags)) continue;         // an earlier window's, or filtered
+        CTO_REQUIRE(rg.lay_out(&r), CTO_EINVAL, "%s", rg.err.c_str());
+        const int64_t end = std::min<int64_t>(int64_t(r.pos) + r.rlen, L);
+        if (end <= r.pos) continue;
+        ++counted;
+        ++diff[size_t(r.pos - w0)];
+        if (end < e1) --diff[size_t(end - w0)];
+        b += std::min(end, e1) - r.pos;
+        if (end > e1) open.push_back(int32_t(end));
+    }
+    int32_t lo = INT32_MAX, hi = INT32_MIN;
+    for (int64_t p = 0; p < n; ++p) {
+        depth += diff[size_t(p)];
+        lo = std::min(lo, depth);
+        hi = std::max(hi, depth);
+    }
+    carry->swap(open);
+    *bases = b; *mn = lo; *mx = hi;
+    if (n_counted) *n_counted = counted;
+    return CTO_OK;
+}
+
+int mix_window_host(const char* const* bams, const char* const* bais, const char* ctg_name, int64_t w0, int64_t w1, const int* m, uint32_t seed,
+                    std::vector<uint8_t>* stream, std::vector<MixRow>* rows, MixCounts* counts) {
+    struct Kept { int32_t pos; std::vector<uint8_t> rec; };
+    std::vector<Kept> kept[2];
+    *counts = MixCounts{};
+    for (int s = 0; s < 2; ++s) {
+        BamRegion rg;
+        CTO_REQUIRE(rg.open("cto_bam_mix", bams[s], bais[s], ctg_name, w0, w1, false, false), CTO_EINVAL, "%s", rg.err.c_str());
+        bool have = false;
+        int prev = 0;
+        for (BamRecord r;;) {
+            const int got = rg.next(&r);
+            CTO_REQUIRE(got >= 0, CTO_EINVAL, "%s", rg.err.c_str());
+            if (got == 0) break;
+            CTO_REQUIRE(!(have && r.pos < prev), CTO_EINVAL, "cto_bam_mix: %s is not coordinate-sorted: position %d of %s behind %d", bams[s],
+                        r.pos + 1, ctg_name, prev + 1);
+            have = true;
+            prev = r.pos;
+            if (r.pos < w0) continue;
+            CTO_REQUIRE(size_t(32) + size_t(r.l_name) + size_t(r.n_cig) * 4 <= rg.rec.size(), CTO_EINVAL,
+                        "cto_bam_mix: alignment record shorter than its fields");
+            ++counts->cand[s];
+            if (!subsample_keeps(subsample_key(rg.rec.data() + 32, std::max(0, r.l_name - 1), seed), m[s])) continue;
+            ++counts->kept[s];
+            kept[s].push_back(Kept{r.pos, rg.rec});
+        }
+    }
+    stream->clear();
+    rows->clear();
+    size_t i = 0, j = 0;
+    while (i < kept[0].size() || j < kept[1].size()) {
+        const bool tumour = j == kept[1].size() || (i < kept[0].size() && kept[0][i].pos <= kept[1][j].pos);     // equal positions: tumour first
+        const Kept& k = tumour ? kept[0][i++] : kept[1][j++];
+        const uint8_t* b = k.rec.data();
+        const int l_name = b[8], n_cig = b[12] | (b[13] << 8);
+        int64_t rlen = 0;
+        for (int c = 0; c < n_cig; ++c) {
+            const uint32_t op = uint32_t(le32(b + 32 + l_name + size_t(c) * 4));
+            if (consumes_ref(int(op & 15))) rlen += int64_t(op >> 4);
+        }
+        rows->push_back(MixRow{k.pos, int32_t(std::min<int64_t>(rlen, INT32_MAX)), b[10] | (b[11] << 8), 0, int64_t(stream->size())});
+        const uint32_t bsz = uint32_t(k.rec.size());
+        const uint8_t h4[4] = {uint8_t(bsz), uint8_t(bsz >> 8), uint8_t(bsz >> 16), uint8_t(bsz >> 24)};
+        stream->insert(stream->end(), h4, h4 + 4);
+        stream->insert(stream->end(), k.rec.begin(), k.rec.end());
+    }
+    return CTO_OK;
+}
+
+namespace {
+constexpr size_t kBgzfPayload = 0xff00;
+// one BGZF block of data[0 .. n) at zlib level 6, stored when the deflated bytes would not fit; false when zlib fails
+bool bgzf_block(z_stream* zs, z_stream* zs0, const uint8_t* data, size_t n, std::vector<uint8_t>* out) {
+    out->resize(18 + 65536 + 8);
+    size_t clen = 0;
+    for (z_stream* z : {zs, zs0}) {
+        deflateReset(z);
+        z->next_in = const_cast<uint8_t*>(data);
+        z->avail_in = uInt(n);
+        z->next_out = out->data() + 18;
+        z->avail_out = 65536;
+        const int rc = deflate(z, Z_FINISH);
+        clen = 65536 - z->avail_out;
+        if (rc == Z_STREAM_END && clen + 26 <= 65536) break;
+        if (z == zs0) return false;
+    }
+    uint8_t* h = out->data();
+    const uint8_t head[16] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 'B', 'C', 2, 0};
+    memcpy(h, head, 16);
+    const uint32_t bs = uint32_t(clen + 25), crc = uint32_t(crc32(crc32(0L, Z_NULL, 0), data, uInt(n)));
+    h[16] = uint8_t(bs); h[17] = uint8_t(bs >> 8);
+    uint8_t* t = h + 18 + clen;
+    for (int k = 0; k < 4; ++k) { t[k] = uint8_t(crc >> (8 * k)); t[4 + k] = uint8_t(uint32_t(n) >> (8 * k)); }
+    out->resize(18 + clen + 8);
+    return true;
+}
+}  // namespace
+
+int MixWriter::open(const char* out_path, const BamHeader& h, int n_threads) {
+    path = out_path;
+    n_ref = int(h.names.size());
+    threads = std::max(1, std::min(n_threads, 64));
+    f = fopen(out_path, "wb");
+    CTO_REQUIRE(f, CTO_EINVAL, "cto_bam_mix: cannot write %s", out_path);
+    pending = h.raw;
+    return CTO_OK;
+}
+
+// writes the whole blocks of `pending` (all: the rest too, then the empty end block)
+int MixWriter::flush(bool all) {
+    const double t0 = now();
+    size_t n_blocks = pending.size() / kBgzfPayload;
+    if (all && pending.size() % kBgzfPayload) ++n_blocks;
+    const size_t n_jobs = n_blocks + (all ? 1 : 0);                 // the end block is a job of no bytes
+    std::vector<std::vector<uint8_t>> out(n_jobs);
+    std::atomic<size_t> next{0};
+    std::atomic<bool> ok{true};
+    auto work = [&] {
+        z_stream zs, zs0;
+        memset(&zs, 0, sizeof zs);
+        memset(&zs0, 0, sizeof zs0);
+        if (deflateInit2(&zs, 6, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) { ok = false; return; }
+        if (deflateInit2(&zs0, 0, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) { deflateEnd(&zs); ok = false; return; }
+        for (size_t k; (k = next.fetch_add(1)) < n_jobs;) {
+            const size_t at = k * kBgzfPayload, n = k < n_blocks ? std::min(kBgzfPayload, pending.size() - at) : 0;
+            if (!bgzf_block(&zs, &zs0, pending.data() + std::min(at, pending.size()), n, &out[k])) ok = false;
+        }
+        deflateEnd(&zs);
+        deflateEnd(&zs0);
+    };
+    const size_t nt = std::min<size_t>(size_t(threads), std::max<size_t>(n_jobs, 1));
+    if (nt <= 1) work();
+    else {
+        std::vector<std::thread> th;
+        for (size_t t = 0; t < nt; ++t) th.emplace_back(work);
+        for (auto& x : th) x.join();
+    }
+    CTO_REQUIRE(ok.load(), CTO_EINVAL, "cto_bam_mix: deflate failed");
+    for (size_t k = 0; k < n_jobs; ++k) {
+        if (k < n_blocks) coff.push_back(file_off);
+        else end_off = file_off;
+        CTO_REQUIRE(fwrite(out[k].data(), 1, out[k].size(), f) == out[k].size(), CTO_EINVAL, "cto_bam_mix: cannot write %s", path.c_str());
+        file_off += int64_t(out[k].size());
+    }
+    const size_t used = std::min(n_blocks * kBgzfPayload, pending.size());
+    pending.erase(pending.begin(), pending.begin() + used);
+    u_pending += int64_t(used);
+    ms += now() - t0;
+    return CTO_OK;
+}
+
+int MixWriter::append(int tid, const uint8_t* stream, size_t n, const MixRow* rows, size_t n_rows) {
+    const int64_t base = u_pending + int64_t(pending.size());
+    for (size_t i = 0; i < n_rows; ++i) {
+        const int64_t u0 = base + rows[i].off, u1 = i + 1 < n_rows ? base + rows[i + 1].off : base + int64_t(n);
+        recs.push_back(Rec{tid, rows[i].pos, rows[i].rlen, rows[i].bin, u0, u1});
+    }
+    pending.insert(pending.end(), stream, stream + n);
+    return pending.size() >= kBgzfPayload ? flush(false) : CTO_OK;
+}
+
+int MixWriter::close(int64_t* out_bytes, int64_t* out_blocks) {
+    const int64_t total = u_pending + int64_t(pending.size());
+    int rc = flush(true);
+    if (rc != CTO_OK) return rc;
+    CTO_REQUIRE(fclose(f) == 0, CTO_EINVAL, "cto_bam_mix: cannot write %s", path.c_str());
+    f = nullptr;
+    if (out_bytes) *out_bytes = total;
+    if (out_blocks) *out_blocks = int64_t(coff.size());
+    // the virtual offset of stream byte u, as a writer names it that flushes whenever 0xff00 bytes are pending
+    auto voff = [&](int64_t u) -> uint64_t {
+        const size_t k = size_t(u / int64_t(kBgzfPayload));
+        return (uint64_t(k < coff.size() ? coff[k] : end_off) << 16) | uint64_t(u % int64_t(kBgzfPayload));
+    };
+    const double t0 = now();
+    std::string bai("BAI\1", 4);
+    auto put32 = [&](uint32_t v) { for (int k = 0; k < 4; ++k) bai += char(uint8_t(v >> (8 * k))); };
+    auto put64 = [&](uint64_t v) { put32(uint32_t(v)); put32(uint32_t(v >> 32)); };
+    put32(uint32_t(n_ref));
+    size_t at = 0;
+    for (int t = 0; t < n_ref; ++t) {
+        std::map<uint32_t, std::vector<Chunk>> bins;
+        std::vector<uint64_t> lin;
+        std::vector<bool> lin_set;
+        for (; at < recs.size() && recs[at].tid == t; ++at) {
+            const Rec& r = recs[at];
+            const uint64_t vb = voff(r.u0), ve = voff(r.u1);
+            std::vector<Chunk>& ch = bins[uint32_t(r.bin)];
+            if (!ch.empty() && ch.back().end == vb) ch.back().end = ve;
+            else ch.push_back(Chunk{vb, ve});
+            const int64_t beg = std::max(r.pos, 0), end = std::max<int64_t>(beg + 1, int64_t(r.pos) + r.rlen);
+            const size_t wl = size_t((end - 1) >> 14);
+            if (lin.size() <= wl) { lin.resize(wl + 1, 0); lin_set.resize(wl + 1, false); }
+            for (size_t w = size_t(beg >> 14); w <= wl; ++w)
+                if (!lin_set[w]) { lin_set[w] = true; lin[w] = vb; }
+        }
+        put32(uint32_t(bins.size()));
+        for (const auto& b : bins) {
+            put32(b.first);
+            put32(uint32_t(b.second.size()));
+            for (const Chunk& c : b.second) { put64(c.beg); put64(c.end); }
+        }
+        put32(uint32_t(lin.size()));
+        uint64_t last = 0;
+        for (size_t w = 0; w < lin.size(); ++w) {
+            if (lin_set[w]) last = lin[w];
+            put64(last);
+        }
+    }
+    const std::string bai_path = path + ".bai";
+    FILE* g = fopen(bai_path.c_str(), "wb");
+    CTO_REQUIRE(g, CTO_EINVAL, "cto_bam_mix: cannot write %s", bai_path.c_str());
+    const bool wrote = fwrite(bai.data(), 1, bai.size(), g) == bai.size();
+    CTO_REQUIRE((fclose(g) == 0) && wrote, CTO_EINVAL, "cto_bam_mix: cannot write %s", bai_path.c_str());
+    ms += now() - t0;
     return CTO_OK;
 }
 

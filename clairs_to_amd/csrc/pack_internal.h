@@ -168,4 +168,51 @@ void phase_merge(const std::vector<PhaseReads>& parts, PhaseReads* out, int64_t*
 void phase_link_host(const PhaseReads& R, int64_t n, int K, int32_t* link);          // link: n x K x 2, zeroed by the call
 void phase_sites(const int32_t* link, const int32_t* pos, int64_t n, int K, int8_t* phase, int32_t* ps, int32_t* block, int64_t* n_blocks);
 void phase_assign_host(const PhaseReads& R, const int8_t* phase, const int32_t* block, const int32_t* ps, uint8_t* hp, int32_t* rps);
+// Coverage, subsample and merge (the C entry points, the rules and the device path: csrc/contam.hip; the host rules, the window plan
+// and the writer of the output BAM and its index: csrc/bam.cpp).  A window [w0, w1) is a run of 16 kb index windows of one contig and
+// owns the records with w0 <= pos < w1.
+constexpr int64_t kContamWindow = 16384;
+constexpr int64_t kContamMaxWindows = 1024;              // per chunk: the depth array of a chunk stays within 16 Mi positions
+constexpr int kCovExclFlags = 1796;                      // mosdepth's default: unmapped, secondary, QC fail, duplicate
+struct BamHeader { std::vector<uint8_t> raw; std::vector<std::string> names; std::vector<int64_t> lens; };   // raw: magic .. reference list
+int contam_read_header(const char* who, const char* bam_path, BamHeader* out);
+// cuts: chunk boundaries in 16 kb windows, 0 .. ceil(L / 16384), so that four times the compressed bytes the sources' linear indices
+// name between two cuts, plus one byte per window (a budget of 1 gives single windows), stay within `budget`
+int contam_plan_windows(const char* who, const char* const* bams, const char* const* bais, int n_src, const char* ctg_name, int64_t L,
+                        int64_t budget, std::vector<int64_t>* cuts);
+// rule b: the 24 bits samtools compares with the fraction, from the read name's n bytes
+inline uint32_t subsample_key(const uint8_t* name, int n, uint32_t seed) {
+    uint32_t h = n > 0 ? name[0] : 0;
+    for (int i = 1; i < n; ++i) h = h * 31u + name[i];
+    uint32_t k = h ^ seed;
+    k += ~(k << 15); k ^= k >> 10; k += k << 3; k ^= k >> 6; k += ~(k << 11); k ^= k >> 16;
+    return k & 0xffffffu;
+}
+inline bool subsample_keeps(uint32_t k24, int m) { return uint64_t(k24) * 1000u < (uint64_t(uint32_t(m)) << 24); }
+// carry: the clipped ends of the spans open at w0 on entry, at w1 on return; *mn / *mx over the window's positions inside the contig
+int cov_window_host(const char* bam_path, const char* bai_path, const char* ctg_name, int64_t w0, int64_t w1, int64_t L, std::vector<int32_t>* carry,
+                    int64_t* bases, int32_t* mn, int32_t* mx, int64_t* n_counted);
+struct MixRow { int32_t pos, rlen, bin, pad_; int64_t off; };      // of a written record: what the index asks; off: in the window's stream
+struct MixCounts { int64_t cand[2], kept[2]; };                    // [0] tumour, [1] normal
+int mix_window_host(const char* const* bams, const char* const* bais, const char* ctg_name, int64_t w0, int64_t w1, const int* m, uint32_t seed,
+                    std::vector<uint8_t>* stream, std::vector<MixRow>* rows, MixCounts* counts);
+// The output file: header + the windows' streams cut into BGZF blocks of 0xff00 bytes, deflated on `threads` threads and written in
+// order; close() writes the end block and <path>.bai from the rows
+struct MixWriter {
+    struct Rec { int32_t tid, pos, rlen, bin; int64_t u0, u1; };
+    FILE* f = nullptr;
+    std::string path;
+    int n_ref = 0, threads = 1;
+    std::vector<uint8_t> pending;        // the stream's bytes behind the last block written
+    int64_t u_pending = 0, file_off = 0; // stream offset of pending[0]; bytes written
+    int64_t end_off = 0;                 // file offset of the empty end block
+    std::vector<int64_t> coff;           // file offset of every block written
+    std::vector<Rec> recs;
+    double ms = 0;
+    ~MixWriter() { if (f) fclose(f); }
+    int open(const char* out_path, const BamHeader& h, int n_threads);
+    int append(int tid, const uint8_t* stream, size_t n, const MixRow* rows, size_t n_rows);
+    int close(int64_t* out_bytes, int64_t* out_blocks);
+    int flush(bool all);
+};
 }  // namespace cto

@@ -918,6 +918,54 @@ int cto_phase_reads(const char* bam_path, const char* bai_path, const char* ctg_
 void cto_phase_result_free(cto_phase_result* r);
 
 /* ----------------------------------------------------------------------------------------------
+ * Contaminated tumour BAMs (csrc/contam.hip; host path csrc/bam.cpp): what src/gen_contaminated_bam.py starts `mosdepth -n -x`,
+ * `samtools view -s`, `samtools merge` and `samtools index` for - per-contig coverage, and a share of a normal BAM mixed into a share
+ * of a tumour BAM.  PARITY UNPINNED against mosdepth and samtools: neither program exists on the build or GPU machines.  The rules
+ * below are the definition (csrc/contam.hip states them in full); all arithmetic is integer, so the device and the host give the same
+ * tables and the same files.
+ *   coverage   of a contig of length L: a record counts when it is the contig's, pos >= 0 and flag & 1796 == 0 (any MAPQ); its span is
+ *              [pos, min(pos + rlen, L)), rlen the reference length of its CIGAR (the CG:B,I tag under the long-CIGAR placeholder);
+ *              nothing inside the CIGAR is looked at, mates are not de-overlapped.  depth(p) = spans that hold p; bases = the sum of
+ *              depth, min / max over p in [0, L); 0 / 0 / 0 without records.
+ *   keep       `samtools view -s SEED.ddd` with the proportion as m thousandths: h = the name's first byte, h = h * 31 + byte for every
+ *              further one (unsigned, without the NUL, mod 2^32; 0 for the empty name); k = h ^ seed; k += ~(k << 15); k ^= k >> 10;
+ *              k += k << 3; k ^= k >> 6; k += ~(k << 11); k ^= k >> 16; kept iff (k & 0xffffff) * 1000 < m * 2^24.  m = 1000 keeps
+ *              every record, m = 0 none (samtools: -s 0.000 switches subsampling off).  No flag or MAPQ filter: every record of the
+ *              contig with pos >= 0 is a candidate, records without a reference are never copied.
+ *   merge      per contig the kept records of both sources ordered by pos, tumour before normal at equal pos, file order within a
+ *              source (samtools also orders equal positions by strand; this does not).  A source whose positions fall within a contig
+ *              is CTO_EINVAL ("not coordinate-sorted").  The header is the tumour's, verbatim; the normal's reference list must equal
+ *              the tumour's (CTO_EINVAL names the first difference).
+ *   output     BAM in BGZF blocks of 0xff00 inflated bytes, zlib level 6 (stored when a block would not fit), the empty end block;
+ *              out_path + ".bai": bins from the records' own bin field, adjacent chunks of a bin joined, 16 kb linear index from pos
+ *              and the CIGAR field's reference length, `0, 0` for contigs without written records.  The bytes do not depend on
+ *              host_threads or on `where`.
+ *   ctg_name   one contig, or NULL: every contig in header order.
+ *   where      0: host; 1: device.  Both walk a contig in position windows - runs of 16 kb index windows cut so that the inflated
+ *              bytes stay under a budget (device 256 MiB, host 2 MiB; CTO_CONTAM_CHUNK_BYTES overrides it, for tests) - a window
+ *              found too large for the device's 32-bit record offsets is halved, down to 16 kb, then CTO_EUNSUPPORTED.  A window whose
+ *              blocks do not inflate, fail their CRC-32 or have a broken record chain is redone by the host path (fallback_chunks).
+ *   host_threads   the threads that deflate the output (0 = one per core, at most 16)
+ *   stats      may be NULL.  ms_inflate = copy up + inflate (host path: reading the windows), ms_kernels = CRC .. gather, ms_copy = the
+ *              copies down (HIP events), ms_write = deflate + write + index (host wall time).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct cto_contam_stats { int64_t n_chunks, n_blocks, inflated_bytes, fallback_chunks, n_records;
+                                  int64_t candidates[2], kept[2];      /* [0] tumour, [1] normal */
+                                  int64_t out_bytes, out_blocks;
+                                  double ms_inflate, ms_kernels, ms_copy, ms_write; } cto_contam_stats;
+typedef struct cto_cov_row { int64_t length, bases; int32_t tid, min, max, pad_; } cto_cov_row;
+/* -> the number of rows written to rows[0 .. cap) (one per contig walked); CTO_ENOMEM when cap is smaller */
+int64_t cto_bam_coverage(const char* bam_path, const char* bai_path, const char* ctg_name /* or NULL */,
+                         int where /* 0 host, 1 device */, int host_threads, void* stream,
+                         cto_cov_row* rows, int64_t cap, cto_contam_stats* stats);
+int cto_bam_mix(const char* tumor_path, const char* tumor_bai, const char* normal_path, const char* normal_bai,
+                const char* ctg_name /* or NULL */, int m_tumor, int m_normal /* thousandths, 0 .. 1000 */, uint32_t seed,
+                const char* out_path, int where /* 0 host, 1 device */, int host_threads, void* stream, cto_contam_stats* stats);
+/* the keep rule on n names laid back to back in `names` (name i: off[i] .. off[i + 1], no NUL): k24[i] = k & 0xffffff, keep[i] = 0 / 1;
+ * either output may be NULL */
+int cto_subsample_keys(const uint8_t* names, const int64_t* off, int64_t n, uint32_t seed, int m, uint32_t* k24, uint8_t* keep);
+
+/* ----------------------------------------------------------------------------------------------
  * Germline genotypes (csrc/germline.hip): the window distances of the reference's predictGermlineGenotypes
  * (src/verdict/predict_germline_genotypes.py:70-154, step 4 of the Verdict chain), over runs of undecided probes.
  *   c               the mirrored BAFs min(baf, 1 - baf) of the undecided probes, run after run, fp64 on the host; no NaN
