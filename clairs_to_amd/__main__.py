@@ -14,6 +14,8 @@ select_hetero_snp_for_phasing and phase_tumor are the long-read steps between ST
 calls of a contig, then their phase and the haplotagged BAM (HP, PS) that haplotype_filtering reads - instead of longphase / whatshap.
 gen_contaminated_bam is the reference's src/gen_contaminated_bam.py: a tumour BAM of a chosen purity from a tumour and a normal BAM -
 coverage, subsample and merge on the GPU instead of mosdepth and samtools.
+add_back_missing_variants_in_genotyping ends a --genotyping_mode_vcf_fn / --hybrid_mode_vcf_fn run: the list's uncalled sites go back into
+the VCF as ./. rows with the depth and A/C/G/T counts of the _hybrid_info files - lines, keys, one sort and the rows' text on the GPU.
     usage: python -m clairs_to_amd compare_vcf --truth_vcf_fn TRUTH --input_vcf_fn CALLS [--bed_fn BED] [--ctg_name CTG] [--output_dir DIR]"""
 import importlib
 import sys
@@ -22,7 +24,7 @@ SUBMODULES = ("extract_candidates_calling", "concat_files", "create_tensor_pileu
               "sort_vcf", "postprocess_vcf", "haplotype_filtering", "realign_reads", "realign_variants",
               "nonsomatic_tagging", "postfilter_variants", "allele_counter", "get_logr_and_baf", "predict_germline_genotypes", "aspcf", "run_ascat",
               "correct_logr", "tag_germline_variant", "cna_germline_tagging", "cal_af_distribution", "compare_vcf",
-              "select_hetero_snp_for_phasing", "phase_tumor", "gen_contaminated_bam")
+              "select_hetero_snp_for_phasing", "phase_tumor", "gen_contaminated_bam", "add_back_missing_variants_in_genotyping")
 
 
 def dispatch(name, argv):

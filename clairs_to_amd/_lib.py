@@ -152,6 +152,11 @@ class CompareStats(C.Structure):
     _fields_ = [("n_input", c_i64), ("n_truth", c_i64), ("n_cutoffs", c_i64), ("host_path", c_i64), ("kernel_ms", C.c_double)]
 
 
+class AddBackStats(C.Structure):
+    _fields_ = [("n_lines", c_i64 * 3), ("n_rows", c_i64), ("undecided", c_i64), ("non_ascii", c_i64), ("bad_source", c_i64), ("bad_line", c_i64),
+                ("host_path", c_i64), ("kernel_ms", C.c_double)]
+
+
 class CompareRecords(C.Structure):
     _fields_ = [(name, c_vp) for name in ("ctg", "pos", "ref_len", "alt_len", "n_alt", "allele", "gt", "qual", "flags")] + [("n", c_i64)]
 
@@ -298,6 +303,9 @@ SYMBOLS = {
     "cto_compare_calls": (C.c_int, [C.POINTER(CompareRecords), C.POINTER(CompareRecords), c_vp, c_vp, C.POINTER(CompareBeds), C.c_int, C.c_int, C.c_int,
                                     C.c_int, c_vp, c_i64, c_vp, c_i64, C.c_int, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.POINTER(CompareStats)]),
     "cto_compare_sweep": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, C.c_int, C.c_int, c_vp, c_vp]),
+    "cto_add_back": (c_i64, [c_vp, C.c_size_t, c_vp, C.c_size_t, c_vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, c_vp, c_vp, C.c_size_t, c_vp,
+                             C.POINTER(AddBackStats)]),
+    "cto_sort_u64": (C.c_int, [c_vp, c_vp, c_i64, C.c_int, c_vp]),
 }
 
 for _name, (_res, _args) in SYMBOLS.items():

@@ -1178,6 +1178,36 @@ int cto_compare_calls(const cto_compare_records* input, const cto_compare_record
 int cto_compare_sweep(const double* values, const uint8_t* sets, int64_t n, const double* cutoffs, int64_t n_cutoffs,
                       int where /* 0 device, 1 host */, int host_threads, void* stream, int64_t* out /* n_cutoffs x 2 */);
 
+/* ----------------------------------------------------------------------------------------------
+ * add_back_missing_variants_in_genotyping (csrc/addback.hip): the reference's last command of a --genotyping_mode_vcf_fn or
+ * --hybrid_mode_vcf_fn run (src/add_back_missing_variants_in_genotyping.py), from the bytes of its inputs to the bytes of its output.
+ * The eleven rules are listed at the top of csrc/addback.hip and derived in DESIGN.md "add_back".
+ *
+ * cto_add_back
+ *   calls, list, info       the inflated text of --call_fn, of the genotyping or hybrid list, and of every `*hybrid_info` file of
+ *                           --candidates_folder back to back (each file ends its last line), on the host; a length of 0 is an absent file
+ *   mode                    0 genotyping (the output's rows are the list's keys), 1 hybrid (the calls' keys and the list's uncalled ones)
+ *   switch_genotype         0 or 1: rewrite an uncalled list row into a ./. row with DP and the A/C/G/T counts of its info line
+ *   where                   0: the kernels, on `stream` (the caller's); 1: the host code of this call on host_threads threads (0: 16)
+ *   out, cap                the output file's bytes, header lines first.  Returns their number; when that exceeds cap nothing was
+ *                           written (call again).  counts: distinct list keys, distinct call keys, list keys not called.
+ *   stats                   required.  n_lines: per text.  non_ascii: a text holds '\r' or a byte >= 0x80; undecided: lines or depth-seqs
+ *                           fields whose numbers Python's int() may read but the plain-digit rule here does not; bad_source (1 calls,
+ *                           2 list) and bad_line (1-based): a line with fewer than two tokens.  With any of them set nothing was
+ *                           written and 0 is returned: the caller decides (the Python module restates the command for the first two and
+ *                           ends the run for the third).  kernel_ms: HIP-event time from the first kernel to the last.
+ * Bytes and integers only: the two paths return the same bytes.  CTO_EINVAL for a null pointer, another mode or `where`;
+ * CTO_EUNSUPPORTED from 4 GB of text or 2^30 lines; CTO_EHIP without a device unless where = 1.  Thread-safe (the device part is serialised).
+ *
+ * cto_sort_u64: the sort of that call alone (csrc/sort.h): n (key, payload) pairs on the host, sorted in place by key, equal keys in
+ * input order - a least-significant-digit radix sort, 8 bits a pass, digits that no two keys differ in skipped; where as above.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct cto_add_back_stats { int64_t n_lines[3], n_rows, undecided, non_ascii, bad_source, bad_line, host_path; double kernel_ms; } cto_add_back_stats;
+int64_t cto_add_back(const uint8_t* calls, size_t n_calls, const uint8_t* list, size_t n_list, const uint8_t* info, size_t n_info,
+                     int mode /* 0 genotyping, 1 hybrid */, int switch_genotype, int where /* 0 device, 1 host */, int host_threads, void* stream,
+                     uint8_t* out, size_t cap, int64_t* counts /* 3 */, cto_add_back_stats* stats);
+int cto_sort_u64(uint64_t* keys, uint32_t* payload, int64_t n, int where /* 0 device, 1 host */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
