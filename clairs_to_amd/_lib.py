@@ -306,6 +306,11 @@ SYMBOLS = {
     "cto_add_back": (c_i64, [c_vp, C.c_size_t, c_vp, C.c_size_t, c_vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, c_vp, c_vp, C.c_size_t, c_vp,
                              C.POINTER(AddBackStats)]),
     "cto_sort_u64": (C.c_int, [c_vp, c_vp, c_i64, C.c_int, c_vp]),
+    "cto_prim_constants": (C.c_int, [c_vp]),
+    "cto_prim_scan": (C.c_int, [c_vp, c_vp, c_i64, C.c_int, C.c_int, C.c_int, c_vp, c_vp, c_vp, c_vp]),
+    "cto_prim_scan_tiles": (C.c_int, [c_vp, c_i64, C.c_int, C.c_int, c_vp, c_vp]),
+    "cto_prim_line_starts": (c_i64, [c_vp, c_i64, C.c_int, C.c_int, c_vp, c_vp, c_i64]),
+    "cto_prim_release": (C.c_int, []),
 }
 
 for _name, (_res, _args) in SYMBOLS.items():

@@ -1,5 +1,7 @@
-// Exclusive prefix sums of int arrays on the device (pileup.hip, extract.hip): one workgroup for short arrays, tile sums / their scan /
-// every tile on top of its base for long ones.  In an anonymous namespace: every translation unit that includes it has its own kernels.
+// Exclusive prefix sums of int arrays on the device: one workgroup for short arrays, tile sums / their scan / every tile on top of its
+// base for long ones.  Included by pileup.hip, extract.hip, allelecount.hip, aftally.hip, hapwindows.hip, phase.hip, contam.hip, pon.hip,
+// addback.hip and comparevcf.hip, directly or through bam_records.h, lines.h and sort.h, and by primitives.hip, whose entries the tests
+// call (tests/test_gpu_primitives.py).  In an anonymous namespace: every translation unit that includes it has its own kernels.
 #pragma once
 #include "common.h"
 

@@ -1208,6 +1208,29 @@ int64_t cto_add_back(const uint8_t* calls, size_t n_calls, const uint8_t* list, 
                      uint8_t* out, size_t cap, int64_t* counts /* 3 */, cto_add_back_stats* stats);
 int cto_sort_u64(uint64_t* keys, uint32_t* payload, int64_t n, int where /* 0 device, 1 host */, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * For the tests only (csrc/primitives.hip): the prefix sums (csrc/scan.h) and line starts (csrc/lines.h) that the device commands share,
+ * reachable alone.  Arrays are on the host.  where: 0 the kernels, on `stream` (the caller's), launched as the commands launch them;
+ * 1 a sequential loop on the host that shares nothing with the kernels.  CTO_EINVAL for a null pointer or an argument outside what is
+ * listed; CTO_EHIP without a device unless where = 1.  Thread-safe (the device part is serialised).
+ *
+ * cto_prim_constants      out[0 .. 3] = SCAN_TILE, SORT_TILE, LINE_TILE, SORT_MAX_N as compiled
+ * cto_prim_scan           out[0, n] = the exclusive prefix sums of in[0, n) and their sum, as int32 (out_bits 32) or int64 (64); n = 0 gives
+ *                         out[0] = 0.  form 0: scan_exclusive; form 1 (32 bits only): k_scan_small in place on its own input, for any n.
+ *                         in2 / out2, when given, are scanned right behind the first on the same stream and scratch.  total, when
+ *                         given, receives the sum of `in` and, with in2, of `in2` behind it, through the kernels' own `total` pointer.
+ * cto_prim_scan_tiles     k_scan_tiles alone: a[i * stride + j], i < n, j < stride <= 3, scanned in place per j; totals[j] = the sums
+ * cto_prim_line_starts    the starts of the lines of text[0, n), ascending, '\n' ending a line and with cr = 1 a '\r' that no '\n' follows
+ *                         too.  Returns their number; when that exceeds cap nothing was written.  CTO_EUNSUPPORTED from 2^32 - LINE_TILE bytes.
+ * cto_prim_release        frees the device buffers these entries keep from call to call
+ * ---------------------------------------------------------------------------------------------- */
+int cto_prim_constants(int64_t* out /* 4 */);
+int cto_prim_scan(const int32_t* in, const int32_t* in2 /* or NULL */, int64_t n, int out_bits /* 32, 64 */, int form, int where, void* stream,
+                  void* out /* n + 1 */, void* out2 /* n + 1, with in2 */, void* total /* NULL, or 1 value (2 with in2) */);
+int cto_prim_scan_tiles(int64_t* a /* n x stride */, int64_t n, int stride, int where, void* stream, int64_t* totals /* stride */);
+int64_t cto_prim_line_starts(const uint8_t* text, int64_t n, int cr, int where, void* stream, uint32_t* starts, int64_t cap);
+int cto_prim_release(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,11 +7,18 @@ import numpy as np
 import pytest
 
 import addbackutil as u
+import primutil as pu
 from conftest import load_json_gz
 
 G = u.golden()
 CONFIGS = {c["name"]: c for c in G["configs"]}
-SORT_TILE = 2048
+SORT_TILE = pu.consts()["SORT_TILE"]          # the library's own, so that the cases below follow the kernels' seams
+LINE_TILE = pu.consts()["LINE_TILE"]
+
+
+def test_the_tile_sizes_are_the_ones_these_cases_were_written_for():
+    """a header that changes them moves every seam here with it: look at the cases again, then at these two numbers"""
+    assert SORT_TILE == 2048 and LINE_TILE == 16384
 
 
 def run_config(cf, d, capsys, where="host", restated=False, monkeypatch=None):
@@ -165,11 +172,31 @@ def test_a_line_without_chrom_and_pos_ends_the_run_naming_it(tmp_path, text, sou
     assert "line %d of %s" % (line, tmp_path / "list.vcf") in str(e.value)
 
 
+SAME = 0x0123456789ABCDEF
+
+
+def one_odd_key(n, at, byte):
+    """every key the same but the one at `at`, which differs in one byte: that pass runs with whole rounds of 64 peers"""
+    keys = np.full(n, SAME, dtype=np.uint64)
+    keys[at] ^= np.uint64(0x5A << (8 * byte))
+    return keys
+
+
 def sort_cases(rng):
-    n_of = (0, 1, SORT_TILE - 1, SORT_TILE, SORT_TILE + 1, 3 * SORT_TILE + 7)
+    T = SORT_TILE
+    # 16 T: the histogram table (256 cells a tile) no longer fits one trip of the one-workgroup scan; 64 T: the scan takes three launches
+    large = (16 * T - 1, 16 * T, 16 * T + 1, 64 * T - 1, 64 * T, 64 * T + 1, 192 * T + 77)
+    n_of = (0, 1, 2, 63, 64, 65, 511, 512, 513, T - 1, T, T + 1, 3 * T + 7) + large
     for n in n_of:
+        i = np.arange(n, dtype=np.uint64)
+        for byte in ((0, 7) if n in large else range(8)):
+            for at in sorted(a for a in {0, n - 1, T - 1, T, 511, 512} if 0 <= a < n):          # first, last, at a tile seam, at a wave seam
+                yield "one_odd_key byte %d at %d" % (byte, at), n, one_odd_key(n, at, byte)
+        for byte in (0, 5):
+            yield "ramp64 byte %d" % byte, n, ((i % np.uint64(256)) << np.uint64(8 * byte)) | np.uint64(0x7766004433221100)
+            yield "groups_of_8 byte %d" % byte, n, (((i // np.uint64(8)) % np.uint64(256)) << np.uint64(8 * byte)) | np.uint64(0x7766004433221100)
         r = rng.integers(0, 1 << 62, n, dtype=np.uint64)
-        yield "equal", n, np.full(n, 0x0123456789ABCDEF, dtype=np.uint64)
+        yield "equal", n, np.full(n, SAME, dtype=np.uint64)
         yield "random", n, r
         yield "few", n, rng.integers(0, 5, n, dtype=np.uint64) * np.uint64(0x0101010101010101)
         yield "sorted", n, np.sort(r)
