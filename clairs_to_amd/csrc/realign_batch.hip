@@ -43,6 +43,7 @@ constexpr int kKmer = 32, kMaxMism = 2;
 constexpr int FP_LMAX = 2048;       // haplotype / reference bytes a window may have on the device path
 constexpr int FP_RMAX = 512;        // read bytes
 constexpr int FP_NT = 256;
+constexpr int FP_CAND = 64;         // diagonals of one (haplotype, read) that wavefronts walk; the ones beyond are walked by the thread that found them
 
 template <int CTRL>
 __device__ __forceinline__ int dpp_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
@@ -93,7 +94,6 @@ __global__ __launch_bounds__(FP_NT) void k_fast_pass(FpArgs a) {
     __shared__ int s_d0_mism, s_dropped;
     // diagonals with a k-mer hit in sight are not walked by the thread that found them - one thread walking 150 positions and marking
     // 150 covered positions while 255 wait - but listed, and every listed diagonal is walked by a wavefront
-    constexpr int FP_CAND = 64;
     __shared__ int s_cand[FP_CAND], s_ncand;
     const int h = blockIdx.x, tid = threadIdx.x;
     const int h0 = a.hap_off[h], L = a.hap_off[h + 1] - h0, w = a.hap_win[h];
@@ -1421,6 +1421,68 @@ extern "C" int cto_ssw_align_batch(int n, const int8_t* codes, size_t n_codes, c
     return cto_realign_write_cigars(text, cigar_buf, cigar_cap, cigar_off);
 }
 CTO_CATCH("cto_ssw_align_batch", int)
+
+extern "C" int cto_fast_pass_limits(int32_t out[4]) try {
+    CTO_REQUIRE(out, CTO_EINVAL, "cto_fast_pass_limits: bad argument");
+    out[0] = FP_LMAX; out[1] = FP_RMAX; out[2] = FP_CAND; out[3] = FP_NT;
+    return CTO_OK;
+}
+CTO_CATCH("cto_fast_pass_limits", int)
+
+// The fast pass of cto_realign_windows on its own (test entry): Window::init, one of the two forms, and what they left in Window::hs -
+// the state collect_pairs() and finish() go on from - copied out.  No rule of the pass is restated here.
+extern "C" int cto_fast_pass_batch(int n_jobs, const cto_realign_job* jobs, int where, int host_threads, void* stream, int32_t* hap_score,
+                                   size_t hap_cap, int32_t* hit_score, int32_t* hit_pos, size_t hit_cap, cto_realign_stats* stats) try {
+    CTO_REQUIRE(n_jobs >= 0 && (jobs || n_jobs == 0) && (hap_score || hap_cap == 0) && ((hit_score && hit_pos) || hit_cap == 0) &&
+                (where == CTO_REALIGN_HOST || where == CTO_REALIGN_DEVICE), CTO_EINVAL, "cto_fast_pass_batch: bad argument");
+    if (stats) memset(stats, 0, sizeof(*stats));
+    const int threads = host_threads > 0 ? host_threads : cto_realign::get_threads();
+    std::vector<Window> ws(static_cast<size_t>(n_jobs));
+    std::vector<Window*> all;
+    for (int i = 0; i < n_jobs; ++i) {
+        const cto_realign_job& j = jobs[i];
+        std::vector<const char*> ps, pc;         // the joined forms, as cto_realign_windows reads them
+        auto split = [&](const char* joined, std::vector<const char*>& v) {
+            v.resize(static_cast<size_t>(std::max(j.n_reads, 0)));
+            for (int r = 0; r < j.n_reads; ++r) { v[size_t(r)] = joined; joined += strlen(joined) + 1; }
+            return v.data();
+        };
+        const char* const* seqs = j.seqs ? j.seqs : (j.seqs_joined ? split(j.seqs_joined, ps) : nullptr);
+        const char* const* cigars = j.cigars ? j.cigars : (j.cigars_joined ? split(j.cigars_joined, pc) : nullptr);
+        const int rc = ws[size_t(i)].init(j.n_reads, seqs, j.positions, cigars, j.reference, j.haplotypes, j.ref_start, j.ref_prefix, j.ref_suffix);
+        if (rc != CTO_OK) { const std::string why = cto_last_error(); cto::set_error("window %d: %s", i, why.c_str()); return rc; }
+        CTO_REQUIRE(where != CTO_REALIGN_DEVICE || device_eligible(ws[size_t(i)]), CTO_EUNSUPPORTED,
+                    "cto_fast_pass_batch: window %d is not one the device form takes (no haplotype, the reference or a haplotype over %d bases, "
+                    "a read over %d)", i, FP_LMAX, FP_RMAX);
+        all.push_back(&ws[size_t(i)]);
+    }
+    size_t n_hap = 0, n_hit = 0;
+    for (const Window& w : ws) { n_hap += size_t(w.n_haps()); n_hit += size_t(w.n_haps()) * size_t(w.n_reads()); }
+    CTO_REQUIRE(n_hap <= hap_cap && n_hit <= hit_cap, CTO_ENOMEM, "cto_fast_pass_batch: %zu haplotypes and %zu hits do not fit the output (%zu, %zu)",
+                n_hap, n_hit, hap_cap, hit_cap);
+    if (where == CTO_REALIGN_DEVICE) {
+        if (!all.empty()) {
+            ArenaLease lease;
+            const int rc = fast_pass_device(all, static_cast<hipStream_t>(stream), threads, stats);
+            if (rc != CTO_OK) return rc;
+        }
+    } else {
+        parallel_for(all.size(), threads, [&](size_t i) { all[i]->fast_pass_host(); });
+    }
+    size_t ha = 0, ht = 0;
+    for (const Window& w : ws)
+        for (const cto_realign::HapState& st : w.hs) {
+            hap_score[ha++] = st.score;
+            for (const cto_realign::ReadHit& hit : st.hits) { hit_score[ht] = hit.score; hit_pos[ht] = hit.position; ++ht; }
+        }
+    if (stats) {
+        stats->windows = n_jobs;
+        for (const Window& w : ws) { stats->reads += w.n_reads(); stats->haplotypes += w.n_haps(); }
+    }
+    reap(std::move(ws));
+    return CTO_OK;
+}
+CTO_CATCH("cto_fast_pass_batch", int)
 
 extern "C" int cto_realign_windows(int n_jobs, cto_realign_job* jobs, int where, int host_threads, void* stream, cto_realign_stats* stats) try {
     CTO_REQUIRE(n_jobs >= 0 && (jobs || n_jobs == 0) && (where == CTO_REALIGN_HOST || where == CTO_REALIGN_DEVICE), CTO_EINVAL,

@@ -201,6 +201,65 @@ def sw_ends_batch(pairs, where="device", threads=0):
     return out
 
 
+def fast_pass_limits():
+    """{FP_LMAX, FP_RMAX, FP_CAND, FP_NT} of k_fast_pass (cto_fast_pass_limits): haplotype and read bytes a window may have on the device
+    path, listed diagonals per (haplotype, read), threads of a workgroup."""
+    out = np.zeros(4, dtype=np.int32)
+    check(lib.cto_fast_pass_limits(out.ctypes.data))
+    return dict(zip(("FP_LMAX", "FP_RMAX", "FP_CAND", "FP_NT"), (int(x) for x in out)))
+
+
+def fast_pass_batch(windows, where, threads=0, stats=None):
+    """The k-mer fast pass alone (cto_fast_pass_batch; test entry): `windows` as for realign_windows; per window the triple
+    (hap_score [H], hit_score [H, n], hit_pos [H, n]) of int32 arrays - the state the later stages start from.  where = "device" runs
+    k_fast_pass and refuses (CTO_EUNSUPPORTED) a window the device form does not take; "host" runs Window::fast_pass_host."""
+    from ._lib import RealignJob, RealignStats
+    n = len(windows)
+    jobs = (RealignJob * max(n, 1))()
+    keep = []
+    n_hap = n_hit = 0
+    for j, w in zip(jobs, windows):
+        seqs, positions, cigars, ref, haps = w[0], w[1], w[2], w[3], w[4]
+        if not (len(seqs) == len(positions) == len(cigars)):
+            raise ValueError("fast_pass_batch: reads, positions and CIGARs of a window must be equally many")
+        if any(len(h.split()) != 1 for h in haps):
+            raise ValueError("fast_pass_batch: a haplotype is empty or holds white space")
+        m = len(seqs)
+        sj, cj = ("\0".join(seqs) + "\0").encode(), ("\0".join(cigars) + "\0").encode()
+        if sj.count(b"\0") != m + (m == 0) or cj.count(b"\0") != m + (m == 0):
+            raise ValueError("fast_pass_batch: a read or CIGAR string with NUL characters")
+        pos = np.asarray(positions, dtype=np.int32).reshape(m)
+        refb, hapb = ref.encode(), " ".join(haps).encode()
+        keep.append((sj, cj, pos, refb, hapb))
+        j.n_reads = m
+        j.seqs, j.cigars = None, None
+        j.seqs_joined, j.cigars_joined = C.cast(C.c_char_p(sj), C.c_void_p).value, C.cast(C.c_char_p(cj), C.c_void_p).value
+        j.positions = pos.ctypes.data if m else None
+        j.reference, j.haplotypes = refb, hapb
+        j.ref_start, j.ref_prefix, j.ref_suffix = w[5], w[6], w[7]
+        n_hap += len(haps)
+        n_hit += len(haps) * m
+    hap_score = np.zeros(max(n_hap, 1), dtype=np.int32)
+    hit_score, hit_pos = np.zeros(max(n_hit, 1), dtype=np.int32), np.zeros(max(n_hit, 1), dtype=np.int32)
+    st = RealignStats()
+    stream = None
+    if where == "device":
+        from ._lib import current_stream_ptr
+        stream = current_stream_ptr()
+    elif where != "host":
+        raise ValueError("fast_pass_batch: where is 'device' or 'host'")
+    check(lib.cto_fast_pass_batch(n, jobs, 1 if where == "device" else 0, int(threads), stream, hap_score.ctypes.data, n_hap,
+                                  hit_score.ctypes.data, hit_pos.ctypes.data, n_hit, C.byref(st)))
+    if stats is not None:
+        stats.update({k: getattr(st, k) for k, _ in RealignStats._fields_})
+    out, ha, ht = [], 0, 0
+    for w in windows:
+        H, m = len(w[4]), len(w[0])
+        out.append((hap_score[ha:ha + H].copy(), hit_score[ht:ht + H * m].reshape(H, m).copy(), hit_pos[ht:ht + H * m].reshape(H, m).copy()))
+        ha, ht = ha + H, ht + H * m
+    return out
+
+
 class WindowBatcher(object):
     """realign_fn of many calls at once.  The reference starts one `realign_reads` process per low-QUAL call and each hands its
     windows to the native realigner one by one (src/realign_variants.py:73-110, src/realign_reads.py:582-595).  Here the calls of

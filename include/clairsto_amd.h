@@ -693,6 +693,17 @@ int cto_sw_ends_batch(int n, const int8_t* codes, size_t n_codes, const int32_t*
  * 1 024 or more than 29 runs are done on the host inside the call); CTO_REALIGN_HOST: host_threads workers.  Same bytes. */
 int cto_ssw_align_batch(int n, const int8_t* codes, size_t n_codes, const int32_t* desc, int where, int host_threads, void* stream,
                         int32_t* score, int32_t* ref_begin, char* cigar_buf, size_t cigar_cap, int64_t* cigar_off);
+/* The fast pass of cto_realign_windows on its own (realigner.cpp:129-229), test entry: the same jobs (their output buffers are not read),
+ * Window::init, then k_fast_pass (where = CTO_REALIGN_DEVICE) or the host form, and the state both leave for the later stages, window after
+ * window in job order: hap_score[H] of a window's H haplotypes (0: dropped or nothing placed), then hit_score / hit_pos [H][n_reads] (0 / -1:
+ * the read is not placed on that haplotype).  hap_cap / hit_cap = elements the outputs hold (CTO_ENOMEM when too few).  With
+ * CTO_REALIGN_DEVICE a window the device form does not take fails the call with CTO_EUNSUPPORTED (the message names it) - nothing goes to the
+ * host, so a call that succeeds ran the kernel.  stats (may be NULL): windows, reads, haplotypes, fast_pairs, fast_pass_ms. */
+int cto_fast_pass_batch(int n_jobs, const cto_realign_job* jobs, int where, int host_threads, void* stream, int32_t* hap_score, size_t hap_cap,
+                        int32_t* hit_score, int32_t* hit_pos, size_t hit_cap, cto_realign_stats* stats);
+/* out = {haplotype / reference bytes, read bytes a window may have on the device path; diagonals of one (haplotype, read) pair that
+ * wavefronts walk before threads walk their own; threads of a k_fast_pass workgroup} */
+int cto_fast_pass_limits(int32_t out[4]);
 /* One striped Smith-Waterman pass alone (ssw.c:118-311 / :341-529 of the reference's src/realign: sw_sse2_byte / sw_sse2_word), test
  * hook: ref / read are base codes 0..4, lanes 16 (bytes) or 8 (words), out[4] = {score (255 on 8-bit overflow), ref_end, read_end,
  * overflow}. */

@@ -30,7 +30,13 @@ what the reference returned, so that those tests hold without oracle/_ref too -
                          120 windows, "thousand": one window of 1 000 reads from seed 7, "device": 400 windows + windows of 300 and
                          1 000 reads, drawn in that order)
 
-Usage: make -C oracle ref && python tests/golden/gen_realign.py [windows|flow|fresh]     (from the repo root; build container only)
+`fastpass` target: the fixed windows of the fast-pass tests (tests/fastpassutil.case_windows: the rules of order at L = 32 .. 200, the
+kernel's limits, the candidate list around its capacity, the batch-layout windows), with what the reference returned on them -
+
+  realign_fastpass.json.gz  {"limits", "inputs_sha256", "windows": {name: [[pos - ref_start, cigar], ...]}}  (a window without reads: [],
+                            the reference's binding is not called for it)
+
+Usage: make -C oracle ref && python tests/golden/gen_realign.py [windows|flow|fresh|fastpass]     (from the repo root; build container only)
 """
 import gzip
 import hashlib
@@ -99,6 +105,31 @@ def gen_fresh():
         with gzip.GzipFile(fileobj=f, mode="wb", mtime=0) as g:
             g.write(raw)
     print("wrote realign_fresh.json.gz: %s windows, %d bytes raw" % ({k: len(v["windows"]) for k, v in out.items()}, len(raw)))
+
+
+def fastpass_digest(cases):
+    h = hashlib.sha256()
+    for name, w in cases.items():
+        h.update(name.encode())
+        window_digest(h, w)
+    return h.hexdigest()
+
+
+def gen_fastpass():
+    import fastpassutil as fp
+    assert ru.ref_lib() is not None, "run `make -C oracle ref` first"
+    lim = fp.limits()
+    cases = fp.case_windows(lim)
+    wins = {}
+    for name, w in cases.items():
+        assert len(w["seqs"]) <= ru.MAX_READS
+        pos, cig = ru.ref_realign(w) if w["seqs"] else ([], [])
+        wins[name] = [[p - w["ref_start"], c] for p, c in zip(pos, cig)]
+    raw = json.dumps({"limits": lim, "inputs_sha256": fastpass_digest(cases), "windows": wins}, separators=(",", ":")).encode()
+    with open(os.path.join(HERE, "realign_fastpass.json.gz"), "wb") as f:
+        with gzip.GzipFile(fileobj=f, mode="wb", mtime=0) as g:
+            g.write(raw)
+    print("wrote realign_fastpass.json.gz: %d windows, %d reads, %d bytes raw" % (len(wins), sum(len(v) for v in wins.values()), len(raw)))
 
 
 def flow_inputs_digest(paths):
@@ -196,3 +227,5 @@ if __name__ == "__main__":
         gen_flow()
     if which in ("all", "fresh"):
         gen_fresh()
+    if which in ("all", "fastpass"):
+        gen_fastpass()
