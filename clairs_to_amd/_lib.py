@@ -106,6 +106,11 @@ class ContamStats(C.Structure):
                 ("ms_inflate", C.c_double), ("ms_kernels", C.c_double), ("ms_copy", C.c_double), ("ms_write", C.c_double)]
 
 
+class DeflateStats(C.Structure):
+    _fields_ = [("n_blocks", c_i64), ("in_bytes", c_i64), ("out_bytes", c_i64), ("stored", c_i64), ("fixed", c_i64), ("dynamic", c_i64),
+                ("ms_kernels", C.c_double)]
+
+
 class CovRow(C.Structure):
     _fields_ = [("length", c_i64), ("bases", c_i64), ("tid", c_i32), ("min", c_i32), ("max", c_i32), ("pad_", c_i32)]
 
@@ -290,6 +295,11 @@ SYMBOLS = {
     "cto_bam_coverage": (c_i64, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, c_vp, C.POINTER(CovRow), c_i64, C.POINTER(ContamStats)]),
     "cto_bam_mix": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_uint32, C.c_char_p, C.c_int, C.c_int,
                               c_vp, C.POINTER(ContamStats)]),
+    "cto_bam_mix_ex": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_uint32, C.c_char_p, C.c_int, C.c_int,
+                                 c_vp, C.POINTER(ContamStats), C.c_int, C.POINTER(DeflateStats)]),
+    "cto_bgzf_deflate": (C.c_int, [c_vp, c_i64, C.c_int, C.c_int, c_vp, c_vp, c_vp, C.POINTER(DeflateStats)]),
+    "cto_deflate_code_lengths": (C.c_int, [c_vp, C.c_int, C.c_int, C.c_int, c_vp]),
+    "cto_deflate_block_sizes": (C.c_int, [c_vp, C.c_int, C.c_int, c_vp, c_vp]),
     "cto_subsample_keys": (C.c_int, [c_vp, c_vp, c_i64, C.c_uint32, C.c_int, c_vp, c_vp]),
     "cto_germline_window_dist": (C.c_int, [c_vp, c_vp, c_i64, C.c_int, C.c_int, c_vp, C.POINTER(GermlineStats)]),
     "cto_aspcf_windows": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, C.c_int, C.c_double, C.c_int, c_vp, c_vp, C.POINTER(AspcfStats)]),

@@ -85,6 +85,51 @@ def inflate_bytes(raw, device):
     return res
 
 
+BGZF_PAYLOAD = 0xff00      # include/clairsto_amd.h: CTO_BGZF_PAYLOAD
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+
+
+def deflate_blocks(raw, where="device", device=None, stream=None, host_threads=0, stats=None):
+    """csrc/deflate.hip: `raw` cut every 0xff00 bytes, every piece one whole BGZF block -> (the blocks back to back as bytes, their sizes
+    as a uint32 array).  where: "device" (the kernels, on `device` / `stream`) or "host" (the same rules on host threads)."""
+    from ._lib import DeflateStats
+    if where not in ("device", "host"):
+        raise ValueError("where must be 'device' or 'host'")
+    src = np.frombuffer(raw, dtype=np.uint8) if not isinstance(raw, np.ndarray) else np.ascontiguousarray(raw, dtype=np.uint8)
+    n = int(src.size)
+    n_blocks = (n + BGZF_PAYLOAD - 1) // BGZF_PAYLOAD
+    st = stats if stats is not None else DeflateStats()
+    if n == 0:
+        return b"", np.zeros(0, dtype=np.uint32)
+    if where == "host":
+        out = np.empty(n_blocks * 65536, dtype=np.uint8)
+        sizes = np.zeros(n_blocks, dtype=np.uint32)
+        check(lib.cto_bgzf_deflate(src.ctypes.data, n, 1, int(host_threads), out.ctypes.data, sizes.ctypes.data, None, C.byref(st)))
+    else:
+        import torch
+        dev = torch.device(device if device is not None else "cuda:0")
+        with torch.cuda.device(dev):
+            s = stream if stream is not None else torch.cuda.current_stream(dev)
+            with torch.cuda.stream(s):
+                d_in = torch.from_numpy(np.array(src)).to(dev)          # a copy: bytes are read-only, torch wants to own
+                d_out = torch.empty(n_blocks * 65536, dtype=torch.uint8, device=dev)
+                d_sizes = torch.zeros(n_blocks, dtype=torch.int32, device=dev)
+                check(lib.cto_bgzf_deflate(d_in.data_ptr(), n, 0, 0, d_out.data_ptr(), d_sizes.data_ptr(), C.c_void_p(s.cuda_stream), C.byref(st)))
+                sizes = d_sizes.cpu().numpy().view(np.uint32)
+                # only the blocks' own bytes come down
+                keep = torch.arange(65536, device=dev, dtype=torch.int32)[None, :] < d_sizes[:, None]
+                packed = d_out.view(n_blocks, 65536)[keep].cpu().numpy()
+            s.synchronize()
+        return packed.tobytes(), sizes
+    out = out.reshape(n_blocks, 65536)
+    return b"".join(out[b, :int(sizes[b])].tobytes() for b in range(n_blocks)), sizes
+
+
+def deflate_bytes(raw, where="device", device=None):
+    """`raw` as a complete BGZF file (the 28-byte end block included), coded by csrc/deflate.hip: the counterpart of inflate_bytes"""
+    return deflate_blocks(raw, where, device)[0] + BGZF_EOF
+
+
 def inflate_span(bam_fn, bai_fn, ctg_name, start, end, device, stream=None):
     """The BGZF blocks holding the alignments that overlap ctg:start-end, inflated on the device and copied back:
     -> (page-locked uint8 host tensor with the inflated blocks, block table).  Runs on `stream` and waits for it."""

@@ -46,6 +46,8 @@
 #include <unordered_map>
 
 #include "bam_host.h"
+#include "deflate_host.h"
+#include "deflate_internal.h"
 #include "hap_internal.h"
 #include "pack_internal.h"
 
@@ -1150,8 +1152,10 @@ bool bgzf_block(z_stream* zs, z_stream* zs0, const uint8_t* data, size_t n, std:
 }
 }  // namespace
 
-int MixWriter::open(const char* out_path, const BamHeader& h, int n_threads) {
+int MixWriter::open(const char* out_path, const BamHeader& h, int n_threads, int deflate_mode, void* hip_stream) {
     path = out_path;
+    coder = deflate_mode;
+    stream = hip_stream;
     n_ref = int(h.names.size());
     threads = std::max(1, std::min(n_threads, 64));
     f = fopen(out_path, "wb");
@@ -1169,7 +1173,34 @@ int MixWriter::flush(bool all) {
     std::vector<std::vector<uint8_t>> out(n_jobs);
     std::atomic<size_t> next{0};
     std::atomic<bool> ok{true};
+    if (coder == 1 && n_blocks) {                                 // up, csrc/deflate.hip, down
+        std::vector<uint8_t> bytes;
+        std::vector<uint32_t> sizes;
+        const int rc = bgzf_deflate_updown(pending.data(), int64_t(std::min(n_blocks * kBgzfPayload, pending.size())), static_cast<hipStream_t>(stream),
+                                           &bytes, &sizes, &dst);
+        if (rc != CTO_OK) return rc;
+        size_t at = 0;
+        for (size_t k = 0; k < n_blocks; ++k) { out[k].assign(bytes.begin() + long(at), bytes.begin() + long(at + sizes[k])); at += sizes[k]; }
+        next = n_blocks;
+    }
     auto work = [&] {
+        if (coder) {                                              // the host restatement (the end block: the same 28 bytes)
+            cto::dfl::BlockInfo info;
+            for (size_t k; (k = next.fetch_add(1)) < n_jobs;) {
+                const size_t at = k * kBgzfPayload, n = k < n_blocks ? std::min(kBgzfPayload, pending.size() - at) : 0;
+                out[k].resize(65536);
+                out[k].resize(size_t(cto::dfl::encode_block(pending.data() + std::min(at, pending.size()), int(n), out[k].data(), &info)));
+                if (k < n_blocks && coder == 2) {
+                    static std::mutex mu;
+                    std::lock_guard<std::mutex> lock(mu);
+                    ++dst.n_blocks;
+                    dst.in_bytes += int64_t(n);
+                    dst.out_bytes += int64_t(out[k].size());
+                    ++(info.type == 0 ? dst.stored : info.type == 1 ? dst.fixed : dst.dynamic);
+                }
+            }
+            return;
+        }
         z_stream zs, zs0;
         memset(&zs, 0, sizeof zs);
         memset(&zs0, 0, sizeof zs0);
@@ -1203,14 +1234,34 @@ int MixWriter::flush(bool all) {
     return CTO_OK;
 }
 
-int MixWriter::append(int tid, const uint8_t* stream, size_t n, const MixRow* rows, size_t n_rows) {
+void MixWriter::add_rows(int tid, size_t n, const MixRow* rows, size_t n_rows) {
     const int64_t base = u_pending + int64_t(pending.size());
     for (size_t i = 0; i < n_rows; ++i) {
         const int64_t u0 = base + rows[i].off, u1 = i + 1 < n_rows ? base + rows[i + 1].off : base + int64_t(n);
         recs.push_back(Rec{tid, rows[i].pos, rows[i].rlen, rows[i].bin, u0, u1});
     }
+}
+
+int MixWriter::append(int tid, const uint8_t* stream, size_t n, const MixRow* rows, size_t n_rows) {
+    add_rows(tid, n, rows, n_rows);
     pending.insert(pending.end(), stream, stream + n);
     return pending.size() >= kBgzfPayload ? flush(false) : CTO_OK;
+}
+
+int MixWriter::append_coded(int tid, size_t n, const MixRow* rows, size_t n_rows, const uint32_t* sizes, size_t n_blocks, const uint8_t* blocks,
+                            const uint8_t* rest, size_t n_rest) {
+    const double t0 = now();
+    CTO_REQUIRE(pending.size() + n == n_blocks * kBgzfPayload + n_rest && n_rest < kBgzfPayload, CTO_EINVAL,
+                "cto_bam_mix: %zu coded blocks and %zu bytes for %zu pending and %zu new bytes", n_blocks, n_rest, pending.size(), n);
+    add_rows(tid, n, rows, n_rows);
+    size_t total = 0;
+    for (size_t k = 0; k < n_blocks; ++k) { coff.push_back(file_off + int64_t(total)); total += sizes[k]; }
+    CTO_REQUIRE(fwrite(blocks, 1, total, f) == total, CTO_EINVAL, "cto_bam_mix: cannot write %s", path.c_str());
+    file_off += int64_t(total);
+    u_pending += int64_t(n_blocks * kBgzfPayload);
+    pending.assign(rest, rest + n_rest);
+    ms += now() - t0;
+    return CTO_OK;
 }
 
 int MixWriter::close(int64_t* out_bytes, int64_t* out_blocks) {

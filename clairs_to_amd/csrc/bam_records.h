@@ -45,42 +45,63 @@ __global__ void k_linearise(const uint8_t* __restrict__ src, const cto_bgzf_bloc
 // runs the byte-table CRC over its own slice (the first slice is the short one, every other one 1024 bytes), lane 0 then chains the
 // 64 partial registers: state after slice k = P_k xor Z(state after slice k-1), Z = "1024 zero bytes" as a 32 x 32 bit matrix
 // (z1k[i] = image of bit i, from the host) - a CRC register is linear in its start value.
-__global__ __launch_bounds__(64) void k_crc32_blocks(const uint8_t* __restrict__ src, const cto_bgzf_block* __restrict__ blocks, int n_blocks,
-                                                     const uint32_t* __restrict__ z1k, Flags* fl) {
-    __shared__ uint32_t table[256];
-    __shared__ uint32_t part[64];
-    __shared__ uint32_t zm[32];
+struct CrcLds { uint32_t table[256], part[64], zm[32]; };
+__device__ __forceinline__ void crc32_wave_setup(CrcLds& L, const uint32_t* __restrict__ z1k) {
     const int lane = threadIdx.x;
     for (int i = lane; i < 256; i += 64) {
         uint32_t c = uint32_t(i);
         for (int k = 0; k < 8; ++k) c = (c & 1u) ? 0xEDB88320u ^ (c >> 1) : c >> 1;
-        table[i] = c;
+        L.table[i] = c;
     }
-    if (lane < 32) zm[lane] = z1k[lane];
+    if (lane < 32) L.zm[lane] = z1k[lane];
     __syncthreads();
+}
+// the CRC-32 of p[0 .. n), 0 < n <= 65536, by the one wave of the workgroup (every lane calls); lane 0 gets the value
+__device__ __forceinline__ uint32_t crc32_wave(CrcLds& L, const uint8_t* __restrict__ p, int n) {
+    const int lane = threadIdx.x;
+    const int ns = (n + 1023) / 1024, r = n - 1024 * (ns - 1);
+    uint32_t c = lane == 0 ? 0xFFFFFFFFu : 0u;
+    if (lane < ns) {
+        const int lo = lane == 0 ? 0 : r + 1024 * (lane - 1), len = lane == 0 ? r : 1024;
+        for (int i = 0; i < len; ++i) c = L.table[(c ^ p[lo + i]) & 0xFFu] ^ (c >> 8);
+    }
+    __syncthreads();
+    L.part[lane] = c;
+    __syncthreads();
+    uint32_t st = 0;
+    if (lane == 0) {
+        st = L.part[0];
+        for (int k = 1; k < ns; ++k) {
+            uint32_t z = 0;
+            for (int i = 0; i < 32; ++i) z ^= ((st >> i) & 1u) ? L.zm[i] : 0u;
+            st = L.part[k] ^ z;
+        }
+    }
+    return st ^ 0xFFFFFFFFu;
+}
+
+__global__ __launch_bounds__(64) void k_crc32_blocks(const uint8_t* __restrict__ src, const cto_bgzf_block* __restrict__ blocks, int n_blocks,
+                                                     const uint32_t* __restrict__ z1k, Flags* fl) {
+    __shared__ CrcLds L;
+    crc32_wave_setup(L, z1k);
     for (int b = blockIdx.x; b < n_blocks; b += gridDim.x) {
         const cto_bgzf_block bd = blocks[b];
         const int n = int(bd.isize);
         if (n == 0) continue;
-        const int ns = (n + 1023) / 1024, r = n - 1024 * (ns - 1);
-        const uint8_t* p = src + bd.out_off;
-        uint32_t c = lane == 0 ? 0xFFFFFFFFu : 0u;
-        if (lane < ns) {
-            const int lo = lane == 0 ? 0 : r + 1024 * (lane - 1), len = lane == 0 ? r : 1024;
-            for (int i = 0; i < len; ++i) c = table[(c ^ p[lo + i]) & 0xFFu] ^ (c >> 8);
-        }
-        __syncthreads();
-        part[lane] = c;
-        __syncthreads();
-        if (lane == 0) {
-            uint32_t st = part[0];
-            for (int k = 1; k < ns; ++k) {
-                uint32_t z = 0;
-                for (int i = 0; i < 32; ++i) z ^= ((st >> i) & 1u) ? zm[i] : 0u;
-                st = part[k] ^ z;
-            }
-            if ((st ^ 0xFFFFFFFFu) != bd.crc32) atomicCAS(&fl->bad_crc, 0, b + 1);
-        }
+        const uint32_t crc = crc32_wave(L, src + bd.out_off, n);
+        if (threadIdx.x == 0 && crc != bd.crc32) atomicCAS(&fl->bad_crc, 0, b + 1);
+    }
+}
+
+// the sibling for a writer: the CRC-32 of every `payload` bytes of src[0 .. n) (the last run shorter) to crc[b]
+__global__ __launch_bounds__(64) void k_crc32_values(const uint8_t* __restrict__ src, int64_t n, int payload, int n_blocks,
+                                                     const uint32_t* __restrict__ z1k, uint32_t* __restrict__ crc) {
+    __shared__ CrcLds L;
+    crc32_wave_setup(L, z1k);
+    for (int b = blockIdx.x; b < n_blocks; b += gridDim.x) {
+        const int64_t at = int64_t(b) * payload;
+        const uint32_t v = crc32_wave(L, src + at, int(min(int64_t(payload), n - at)));
+        if (threadIdx.x == 0) crc[b] = v;
     }
 }
 

@@ -66,6 +66,7 @@
 #include <vector>
 #include "bam_records.h"
 #include "common.h"
+#include "deflate_internal.h"
 #include "hip_buffers.h"
 #include "inflated_span.h"
 #include "pack_internal.h"
@@ -339,7 +340,8 @@ struct ContamCtx {
     Source src[2];
     DevBuf cpos, cend, open, diff, psum, ends;                      // coverage
     DevBuf rlen, rsrc, roff, out, rows;                             // mix
-    PinBuf h_cov, h_out, h_rows;
+    DevBuf d_slots, d_packed;                                       // mix with the device coder: its blocks in slots, back to back
+    PinBuf h_cov, h_out, h_rows, h_coded;
     Event t[5];
 };
 
@@ -407,8 +409,12 @@ int cov_window_device(ContamCtx* cx, const char* bam_path, const char* bai_path,
 }
 
 // Rules b and c over the window [w0, w1) on the device: the merged stream and its rows in cx->h_out / cx->h_rows
+// carry (deflate on the device, else null): the bytes the writer holds behind its last block go up in front of the merged stream, the
+// whole blocks of both are coded here (csrc/deflate.hip) and come down in *coded; the bytes behind them are in cx->h_out
+struct CodedDown { const uint32_t* sizes = nullptr; const uint8_t* blocks = nullptr; int64_t n_blocks = 0, n_rest = 0; };
 int mix_window_device(ContamCtx* cx, const char* const* bams, const char* const* bais, const char* ctg_name, int64_t w0, int64_t w1, const int* m,
-                      uint32_t seed, hipStream_t s, cto_contam_stats* st, int64_t* n_bytes, int64_t* n_rows, MixCounts* counts, int* outcome) {
+                      uint32_t seed, hipStream_t s, cto_contam_stats* st, int64_t* n_bytes, int64_t* n_rows, MixCounts* counts, int* outcome,
+                      const std::vector<uint8_t>* carry = nullptr, CodedDown* coded = nullptr, cto_deflate_stats* dst = nullptr) {
     *n_bytes = *n_rows = 0;
     *counts = MixCounts{};
     int rc;
@@ -458,22 +464,48 @@ int mix_window_device(ContamCtx* cx, const char* const* bams, const char* const*
     RecordStream& rs = const_cast<RecordStream&>(lead.rs);
     int64_t room = 0;
     for (int k = 0; k < 2; ++k) if (!cx->src[k].empty) room += cx->src[k].tables.len;
+    // the stream starts at a multiple of 4 (k_gather), the carried bytes end there
+    const size_t n_carry = carry ? carry->size() : 0, slack = (4 - (n_carry & 3)) & 3;
     if ((rc = cx->rlen.ensure(size_t(n_out) * 4)) || (rc = cx->rsrc.ensure(size_t(n_out) * 4)) || (rc = cx->roff.ensure(size_t(n_out + 1) * 8)) ||
-        (rc = cx->out.ensure(size_t(room) + 64)) || (rc = cx->rows.ensure(size_t(n_out) * sizeof(MixRow))))
+        (rc = cx->out.ensure(slack + n_carry + size_t(room) + 64)) || (rc = cx->rows.ensure(size_t(n_out) * sizeof(MixRow))))
         return rc;
+    uint8_t* const d_stream = cx->out.as<uint8_t>() + slack + n_carry;
+    if (n_carry) CTO_HIP(hipMemcpyAsync(cx->out.as<uint8_t>() + slack, carry->data(), n_carry, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_merge_rank, dim3(unsigned(cdiv(n_out, 128))), dim3(128), 0, s, ks[0], ks[1], cx->rlen.as<int>(), cx->rsrc.as<uint32_t>());
     if ((rc = rs.scan(s, cx->rlen.as<int>(), int(n_out), cx->roff.as<long long>(), &rs.fl->n_entries))) return rc;
     hipLaunchKernelGGL(k_gather, dim3(unsigned(cdiv(n_out, 4))), dim3(256), 0, s, ks[0], ks[1], cx->rsrc.as<uint32_t>(), cx->roff.as<long long>(),
-                       int(n_out), cx->out.as<uint8_t>(), cx->rows.as<MixRow>());
+                       int(n_out), d_stream, cx->rows.as<MixRow>());
     CTO_HIP(hipGetLastError());
     CTO_HIP(hipEventRecord(cx->t[2], s));
     if ((rc = rs.fetch_flags(s))) return rc;
     const int64_t total = rs.h_flags.as<Flags>()->n_entries;
     CTO_REQUIRE(total >= 0 && total <= room, CTO_EINVAL, "cto_bam_mix: the merged window has %lld bytes, its sources %lld", (long long)total,
                 (long long)room);
+    if (coded) {
+        const int64_t all = int64_t(n_carry) + total, whole = all / CTO_BGZF_PAYLOAD * CTO_BGZF_PAYLOAD;
+        const uint8_t* d_in = cx->out.as<uint8_t>() + slack;
+        int64_t n_coded = 0;
+        double ms_down = 0;
+        if ((rc = bgzf_deflate_down(d_in, whole, s, &cx->d_slots, &cx->d_packed, &cx->h_coded, &coded->sizes, &coded->blocks, &n_coded, dst, &ms_down)))
+            return rc;
+        coded->n_blocks = whole / CTO_BGZF_PAYLOAD;
+        coded->n_rest = all - whole;
+        if ((rc = cx->h_out.ensure(size_t(coded->n_rest) + 64)) || (rc = cx->h_rows.ensure(size_t(n_out) * sizeof(MixRow)))) return rc;
+        CTO_HIP(hipEventRecord(cx->t[3], s));
+        if (coded->n_rest) CTO_HIP(hipMemcpyAsync(cx->h_out.p, d_in + whole, size_t(coded->n_rest), hipMemcpyDeviceToHost, s));
+        CTO_HIP(hipMemcpyAsync(cx->h_rows.p, cx->rows.p, size_t(n_out) * sizeof(MixRow), hipMemcpyDeviceToHost, s));
+        CTO_HIP(hipEventRecord(cx->t[4], s));
+        if ((rc = rs.wait(s))) return rc;
+        *n_bytes = total;
+        *n_rows = n_out;
+        st->ms_inflate += elapsed(cx->t[0], cx->t[1]);
+        st->ms_kernels += elapsed(cx->t[1], cx->t[2]);
+        st->ms_copy += ms_down + elapsed(cx->t[3], cx->t[4]);
+        return CTO_OK;
+    }
     if ((rc = cx->h_out.ensure(size_t(total) + 64)) || (rc = cx->h_rows.ensure(size_t(n_out) * sizeof(MixRow)))) return rc;
     CTO_HIP(hipEventRecord(cx->t[3], s));
-    CTO_HIP(hipMemcpyAsync(cx->h_out.p, cx->out.p, size_t(total), hipMemcpyDeviceToHost, s));
+    CTO_HIP(hipMemcpyAsync(cx->h_out.p, d_stream, size_t(total), hipMemcpyDeviceToHost, s));
     CTO_HIP(hipMemcpyAsync(cx->h_rows.p, cx->rows.p, size_t(n_out) * sizeof(MixRow), hipMemcpyDeviceToHost, s));
     CTO_HIP(hipEventRecord(cx->t[4], s));
     if ((rc = rs.wait(s))) return rc;
@@ -597,7 +629,16 @@ extern "C" int64_t cto_bam_coverage(const char* bam_path, const char* bai_path, 
 extern "C" int cto_bam_mix(const char* tumor_path, const char* tumor_bai, const char* normal_path, const char* normal_bai, const char* ctg_name,
                            int m_tumor, int m_normal, uint32_t seed, const char* out_path, int where, int host_threads, void* stream,
                            cto_contam_stats* stats) {
+    return cto_bam_mix_ex(tumor_path, tumor_bai, normal_path, normal_bai, ctg_name, m_tumor, m_normal, seed, out_path, where, host_threads, stream,
+                          stats, 0, nullptr);
+}
+
+extern "C" int cto_bam_mix_ex(const char* tumor_path, const char* tumor_bai, const char* normal_path, const char* normal_bai, const char* ctg_name,
+                              int m_tumor, int m_normal, uint32_t seed, const char* out_path, int where, int host_threads, void* stream,
+                              cto_contam_stats* stats, int deflate, cto_deflate_stats* dstats) {
     return guarded("cto_bam_mix", [&]() -> int {
+        CTO_REQUIRE(deflate >= 0 && deflate <= 2, CTO_EINVAL, "cto_bam_mix: deflate must be 0 (zlib), 1 (device coder) or 2 (its host restatement)");
+        if (dstats) *dstats = cto_deflate_stats{};
         CTO_REQUIRE(tumor_path && normal_path && out_path, CTO_EINVAL, "cto_bam_mix: null argument");
         CTO_REQUIRE(where == 0 || where == 1, CTO_EINVAL, "cto_bam_mix: where must be 0 (host) or 1 (device)");
         CTO_REQUIRE(m_tumor >= 0 && m_tumor <= 1000 && m_normal >= 0 && m_normal <= 1000, CTO_EINVAL,
@@ -637,7 +678,8 @@ extern "C" int cto_bam_mix(const char* tumor_path, const char* tumor_bai, const 
             for (Event& e : cx->t) if (!e && (rc = e.create())) return rc;
         }
         MixWriter wr;
-        if ((rc = wr.open(out_path, h, thread_count(host_threads)))) return rc;
+        if ((rc = wr.open(out_path, h, thread_count(host_threads), deflate, stream))) return rc;
+        const bool code_here = where == 1 && deflate == 1;           // the stream never comes down: its blocks do
         std::vector<uint8_t> stream_bytes;
         std::vector<MixRow> rows;
         for (size_t k = 0; k < tids.size(); ++k) {
@@ -651,7 +693,10 @@ extern "C" int cto_bam_mix(const char* tumor_path, const char* tumor_bai, const 
                 int outcome = where == 1 ? CHUNK_DONE : CHUNK_NOTHING;
                 int64_t n_bytes = 0, n_rows = 0;
                 MixCounts counts{};
-                if (where == 1 && (rc = mix_window_device(cx, bams, bais, ctg, w0, w1, m, seed, s, &st, &n_bytes, &n_rows, &counts, &outcome))) return rc;
+                CodedDown coded;
+                if (where == 1 && (rc = mix_window_device(cx, bams, bais, ctg, w0, w1, m, seed, s, &st, &n_bytes, &n_rows, &counts, &outcome,
+                                                          code_here ? &wr.pending : nullptr, code_here ? &coded : nullptr, &wr.dst)))
+                    return rc;
                 if (outcome == CHUNK_TOO_LARGE) {
                     CTO_REQUIRE(b - a > 1, CTO_EUNSUPPORTED, "cto_bam_mix: more than 4 GiB of alignment records over one 16 kb window");
                     todo.push_back({a + (b - a) / 2, b});
@@ -659,7 +704,11 @@ extern "C" int cto_bam_mix(const char* tumor_path, const char* tumor_bai, const 
                     continue;
                 }
                 ++st.n_chunks;
-                if (outcome == CHUNK_DONE) {
+                if (outcome == CHUNK_DONE && code_here && n_bytes) {
+                    if ((rc = wr.append_coded(t, size_t(n_bytes), cx->h_rows.as<MixRow>(), size_t(n_rows), coded.sizes, size_t(coded.n_blocks), coded.blocks,
+                                              cx->h_out.as<uint8_t>(), size_t(coded.n_rest))))
+                        return rc;
+                } else if (outcome == CHUNK_DONE) {
                     if ((rc = wr.append(t, cx->h_out.as<uint8_t>(), size_t(n_bytes), cx->h_rows.as<MixRow>(), size_t(n_rows)))) return rc;
                 } else {
                     const double t0 = now_ms();
@@ -675,6 +724,7 @@ extern "C" int cto_bam_mix(const char* tumor_path, const char* tumor_bai, const 
         if ((rc = wr.close(&st.out_bytes, &st.out_blocks))) return rc;
         st.ms_write = wr.ms;
         if (stats) *stats = st;
+        if (dstats) *dstats = wr.dst;
         return CTO_OK;
     });
 }

@@ -197,7 +197,9 @@ struct MixCounts { int64_t cand[2], kept[2]; };                    // [0] tumour
 int mix_window_host(const char* const* bams, const char* const* bais, const char* ctg_name, int64_t w0, int64_t w1, const int* m, uint32_t seed,
                     std::vector<uint8_t>* stream, std::vector<MixRow>* rows, MixCounts* counts);
 // The output file: header + the windows' streams cut into BGZF blocks of 0xff00 bytes, deflated on `threads` threads and written in
-// order; close() writes the end block and <path>.bai from the rows
+// order; close() writes the end block and <path>.bai from the rows.  coder: 0 zlib level 6; 1 csrc/deflate.hip on the device (bytes
+// appended on the host go up and the blocks come down; append_coded takes blocks coded where the stream was built); 2 its host
+// restatement on the threads.  1 and 2 write the same bytes.
 struct MixWriter {
     struct Rec { int32_t tid, pos, rlen, bin; int64_t u0, u1; };
     FILE* f = nullptr;
@@ -209,9 +211,17 @@ struct MixWriter {
     std::vector<int64_t> coff;           // file offset of every block written
     std::vector<Rec> recs;
     double ms = 0;
+    int coder = 0;
+    void* stream = nullptr;              // hipStream_t of coder 1
+    cto_deflate_stats dst{};
     ~MixWriter() { if (f) fclose(f); }
-    int open(const char* out_path, const BamHeader& h, int n_threads);
+    int open(const char* out_path, const BamHeader& h, int n_threads, int deflate_mode = 0, void* hip_stream = nullptr);
     int append(int tid, const uint8_t* stream, size_t n, const MixRow* rows, size_t n_rows);
+    // a window of n stream bytes whose whole blocks, counted from pending[0], are coded already: n_blocks blocks back to back in
+    // `blocks`, and the n_rest bytes behind them, which become the new pending
+    int append_coded(int tid, size_t n, const MixRow* rows, size_t n_rows, const uint32_t* sizes, size_t n_blocks, const uint8_t* blocks,
+                     const uint8_t* rest, size_t n_rest);
+    void add_rows(int tid, size_t n, const MixRow* rows, size_t n_rows);
     int close(int64_t* out_bytes, int64_t* out_blocks);
     int flush(bool all);
 };

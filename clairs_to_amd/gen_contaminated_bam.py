@@ -6,6 +6,11 @@ are this package's own (csrc/contam.hip lists them).
 
     python -m clairs_to_amd gen_contaminated_bam --normal_bam_fn N.bam --tumor_bam_fn T.bam --output_dir DIR --tumor_purity 0.5
         [--normal_bam_coverage X] [--tumor_bam_coverage Y] [--ctg_name CTG] [--cal_output_bam_coverage 1] [--seed 0] [--where device|host]
+        [--deflate zlib|device|host]
+
+--deflate chooses the coder of the output's BGZF blocks: zlib level 6 on the host threads (the default), csrc/deflate.hip on the device
+(with --where device the merged stream never comes down, only its compressed blocks do), or that coder's host restatement.  The last
+two write the same bytes; the records, the block cuts and the index rules are those of zlib's file.
 
 The options are the reference parser's.  The lines that carry values are printed as the reference prints them; its "Will run the following
 commands" lines are not, since no command is run.  A coverage that is not given is computed and written where the reference expects
@@ -23,6 +28,7 @@ from argparse import ArgumentParser
 from ._cli import add_ignored, str2bool, str_none
 
 COV_SUFFIX = ".cov.mosdepth.summary.txt"
+DEFLATE_MODES = ("zlib", "device", "host")          # cto_bam_mix_ex's deflate: 0, 1, 2
 MAX_THREADS = 16
 
 
@@ -92,17 +98,26 @@ def bam_coverage(bam, ctg=None, where="device", bai=None, host_threads=0, stats=
 
 
 def mix_bams(tumor_bam, normal_bam, out_bam, m_tumor, m_normal, seed=0, ctg=None, where="device", tumor_bai=None, normal_bai=None,
-             host_threads=0, stats=None):
+             host_threads=0, stats=None, deflate="zlib", deflate_stats=None):
     """cto_bam_mix: `samtools view -s SEED.ddd` of both BAMs and `samtools merge` + `samtools index` of what is kept, in one pass, into
     out_bam and out_bam + '.bai'.  m_tumor / m_normal: the proportions in thousandths, 0 .. 1000 (the reference's "%.3f" strings); 1000
     keeps every record, as -s 1.000 does, and 0 keeps none - unlike samtools, where -s 0.000 switches subsampling off and keeps all.
-    ctg: one contig, or None for every contig in header order.  -> dict(candidates [tumour, normal], kept [tumour, normal])"""
-    from ._lib import ContamStats, check, lib
+    ctg: one contig, or None for every contig in header order.  deflate: the coder of the output's blocks, "zlib" (level 6), "device"
+    (csrc/deflate.hip) or "host" (its host restatement; the same bytes as "device"); deflate_stats: a dict that receives its
+    cto_deflate_stats.  -> dict(candidates [tumour, normal], kept [tumour, normal])"""
+    from ._lib import ContamStats, DeflateStats, check, lib
     w, stream = _where_args(where)
-    st = ContamStats()
-    check(lib.cto_bam_mix(_path(tumor_bam), _path(tumor_bai), _path(normal_bam), _path(normal_bai), ctg.encode() if ctg is not None else None,
-                          int(m_tumor), int(m_normal), int(seed) & 0xffffffff, _path(out_bam), w, int(host_threads), stream, C.byref(st)))
+    if deflate not in DEFLATE_MODES:
+        raise ValueError("deflate must be one of %s" % ", ".join(DEFLATE_MODES))
+    st, dst = ContamStats(), DeflateStats()
+    if deflate == "device" and stream is None:
+        from ._lib import current_stream_ptr
+        stream = C.c_void_p(current_stream_ptr())
+    check(lib.cto_bam_mix_ex(_path(tumor_bam), _path(tumor_bai), _path(normal_bam), _path(normal_bai), ctg.encode() if ctg is not None else None,
+                             int(m_tumor), int(m_normal), int(seed) & 0xffffffff, _path(out_bam), w, int(host_threads), stream, C.byref(st),
+                             DEFLATE_MODES.index(deflate), C.byref(dst)))
     _stats_into(stats, st)
+    _stats_into(deflate_stats, dst)
     return dict(candidates=[int(st.candidates[0]), int(st.candidates[1])], kept=[int(st.kept[0]), int(st.kept[1])])
 
 
@@ -184,8 +199,9 @@ def gen_contaminated_bam(args):
         for name, v in (("normal", m_normal), ("tumor", m_tumor)):
             if not 0 <= v <= 1000:
                 sys.exit("gen_contaminated_bam: the {} subsample proportion {} is outside 0 .. 1".format(name, v / 1000.0))
+        print("[INFO] BGZF deflate of the output: {}".format(args.deflate))
         res = mix_bams(args.tumor_bam_fn, args.normal_bam_fn, out_bam, m_tumor, m_normal, seed=args.seed, ctg=args.ctg_name, where=where,
-                       host_threads=args.samtools_threads)
+                       host_threads=args.samtools_threads, deflate=args.deflate)
         if args.cal_output_bam_coverage:
             coverage_of(args, out_bam, True, where, os.path.join(output_dir, "cov"))
         if args.remove_intermediate_dir:
@@ -208,6 +224,8 @@ def build_parser():
     ap.add_argument("--cal_output_bam_coverage", type=str2bool, default=0, help="EXPERIMENTAL: calculate the coverage of the output BAM")
     ap.add_argument("--remove_intermediate_dir", action="store_true", help="Remove intermediate directory. Default: False")
     ap.add_argument("--where", type=str, default=None, choices=("device", "host"), help="Where the BAMs are read, default: device when there is one")
+    ap.add_argument("--deflate", type=str, default="zlib", choices=DEFLATE_MODES,
+                    help="The coder of the output's BGZF blocks: zlib level 6, the device coder, or its host restatement, default: %(default)s")
     ap.add_argument("--seed", type=int, default=0, help="The subsampling seed: the integer part of the reference's `-s 0.ddd`, default: %(default)d")
     add_ignored(ap, samtools="str", mosdepth="str")
     return ap

@@ -234,6 +234,49 @@ class BgzfWriter(object):
         self.f.close()
 
 
+class BatchBgzfWriter(object):
+    """The same blocks through csrc/deflate.hip (where: "device", or "host" for its host restatement), up to BATCH of them per
+    cto_bgzf_deflate call.  A block's file offset is not known while it waits for its batch, so tell() names the next byte in
+    block-index space, (block index << 16) | offset in the block; file_voff() turns such an offset into a virtual file offset once
+    close() has written everything."""
+    PAYLOAD = 0xff00
+    BATCH = 256
+
+    def __init__(self, path, where="device", device=None):
+        self.f, self.where, self.device = open(path, "wb"), where, device
+        self.buf, self.n_done, self.block_off, self.coff = bytearray(), 0, [], 0
+
+    def _code(self, n_bytes):
+        from .bgzf import deflate_blocks
+        data = bytes(self.buf[:n_bytes])
+        del self.buf[:n_bytes]
+        blocks, sizes = deflate_blocks(data, self.where, self.device)
+        for sz in sizes:
+            self.block_off.append(self.coff)
+            self.coff += int(sz)
+        self.n_done += len(sizes)
+        self.f.write(blocks)
+
+    def tell(self):
+        return ((self.n_done + len(self.buf) // self.PAYLOAD) << 16) | (len(self.buf) % self.PAYLOAD)
+
+    def write(self, data):
+        self.buf += data
+        if len(self.buf) >= self.BATCH * self.PAYLOAD:
+            self._code(len(self.buf) // self.PAYLOAD * self.PAYLOAD)
+
+    def close(self):
+        from .bgzf import BGZF_EOF
+        if self.buf:
+            self._code(len(self.buf))
+        self.block_off.append(self.coff)                # the empty block that ends the file
+        self.f.write(BGZF_EOF)
+        self.f.close()
+
+    def file_voff(self, v):
+        return (self.block_off[v >> 16] << 16) | (v & 0xffff)
+
+
 _AUX_SIZE = {"A": 1, "c": 1, "C": 1, "s": 2, "S": 2, "i": 4, "I": 4, "f": 4}
 
 
@@ -289,10 +332,13 @@ def _first_offset(bai_fn, tid):
 _CONSUMES_REF = (0, 2, 3, 7, 8)
 
 
-def haplotag_bam(bam_fn, bai_fn, ctg, tags, out_fn, level=6):
+def haplotag_bam(bam_fn, bai_fn, ctg, tags, out_fn, level=6, deflate="zlib", device=None):
     """Writes out_fn and out_fn + '.bai': the header of bam_fn, verbatim, and every record of contig `ctg` in file order - the ones that
     did not enter the phasing too - without the HP and PS fields it came with, and with HP:i / PS:i appended where tags names its
-    virtual offset: {voff: (hp, ps)}.  The index: bins from the records' own bin field, 16 kb linear index.  -> (records, tagged)"""
+    virtual offset: {voff: (hp, ps)}.  The index: bins from the records' own bin field, 16 kb linear index.  deflate: "zlib" (level
+    `level`), or "device" / "host" for csrc/deflate.hip and its host restatement (the same bytes from both).  -> (records, tagged)"""
+    if deflate not in ("zlib", "device", "host"):
+        raise ValueError("phase_tumor: deflate must be zlib, device or host")
     rd = BgzfReader(bam_fn)
     try:
         head = rd.read(8)
@@ -310,7 +356,7 @@ def haplotag_bam(bam_fn, bai_fn, ctg, tags, out_fn, level=6):
                 tid = r
         if tid < 0:
             raise ValueError("phase_tumor: contig %s not in the BAM header" % ctg)
-        wr = BgzfWriter(out_fn, level)
+        wr = BgzfWriter(out_fn, level) if deflate == "zlib" else BatchBgzfWriter(out_fn, deflate, device)
         wr.write(header)
         bins, lin = {}, {}
         n_rec = n_tag = 0
@@ -350,6 +396,9 @@ def haplotag_bam(bam_fn, bai_fn, ctg, tags, out_fn, level=6):
                 for w in range(beg >> 14, ((end - 1) >> 14) + 1):
                     lin.setdefault(w, vb)
         wr.close()
+        if deflate != "zlib":                           # block-index space -> file offsets, now that every block has its size
+            bins = {b: [[wr.file_voff(vb), wr.file_voff(ve)] for vb, ve in chunks] for b, chunks in bins.items()}
+            lin = {w: wr.file_voff(v) for w, v in lin.items()}
     finally:
         rd.close()
     out = b"BAI\1" + struct.pack("<i", n_ref)
@@ -384,9 +433,12 @@ def phase_tumor(args):
             os.makedirs(os.path.dirname(fn), exist_ok=True)
     write_vcf_gz(args.output_vcf_fn, phased_rows(rows, sites, res["phase"], res["ps"]))
     tags = {int(v): (int(h), int(p)) for v, h, p in zip(res["voff"], res["hp"], res["read_ps"]) if h}
-    n_rec, n_tag = haplotag_bam(args.tumor_bam_fn, bai, args.ctg_name, tags, args.output_bam_fn)
+    deflate = getattr(args, "deflate", None) or "zlib"
+    n_rec, n_tag = haplotag_bam(args.tumor_bam_fn, bai, args.ctg_name, tags, args.output_bam_fn, deflate=deflate)
     print("[INFO] phase_tumor %s: %d of %d sites phased in %d blocks; %d of %d reads tagged (%d entered); %s path" % (
         args.ctg_name, int((res["phase"] >= 0).sum()), len(sites), stats.get("n_phase_blocks", 0), n_tag, n_rec, len(res["voff"]), where))
+    if deflate != "zlib":
+        print("[INFO] phase_tumor %s: BGZF deflate of the output BAM: %s" % (args.ctg_name, deflate))
     return res
 
 
@@ -404,6 +456,8 @@ def build_parser():
     ap.add_argument("--link_span", type=int, default=LINK_SPAN, help="How many sites ahead a site is linked to, default: %(default)d")
     ap.add_argument("--where", type=str, default=None, choices=("device", "host"), help="Where the reads are phased, default: device when there is one")
     ap.add_argument("--threads", type=int, default=0, help="Threads of the host path, default: one per core, at most 32")
+    ap.add_argument("--deflate", type=str, default="zlib", choices=("zlib", "device", "host"), help="The coder of the output BAM's BGZF blocks: "
+                    "zlib level 6, the device coder (csrc/deflate.hip), or its host restatement, default: %(default)s")
     return ap
 
 

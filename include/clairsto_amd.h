@@ -977,6 +977,38 @@ int cto_bam_mix(const char* tumor_path, const char* tumor_bai, const char* norma
 int cto_subsample_keys(const uint8_t* names, const int64_t* off, int64_t n, uint32_t seed, int m, uint32_t* k24, uint8_t* keep);
 
 /* ----------------------------------------------------------------------------------------------
+ * BGZF deflate (csrc/deflate.hip; host restatement csrc/deflate_host.h): the counterpart of cto_bgzf_inflate for the BAMs the package
+ * writes.  The input is cut every CTO_BGZF_PAYLOAD bytes (the last block shorter); each piece becomes one whole BGZF block - header,
+ * one final DEFLATE block (stored, fixed-Huffman or dynamic-Huffman, whichever has the fewest bits; stored before fixed before dynamic
+ * on a tie), CRC-32, ISIZE - of at most n + 31 bytes.  The parse (hash candidates per tile of 256 positions plus a few short
+ * distances, greedy within segments of 512 bytes) and the length-limited code construction are stated in full in csrc/deflate.hip;
+ * the output is a pure function of the input bytes, the same from the device and from the host path.
+ *   where        0: device - in, out and sizes are device pointers, the kernels run on `stream` and the call waits for them;
+ *                1: host - host pointers, the blocks spread over host_threads threads (0 = one per core, at most 16)
+ *   out          n_blocks = ceil(n / CTO_BGZF_PAYLOAD) slots of 65536 bytes; sizes[b] = the whole size of block b in its slot
+ *   n == 0       no blocks (the empty end block of a file is the writer's)
+ *   stats        may be NULL; ms_kernels (HIP events) only from the device
+ * cto_deflate_code_lengths and cto_deflate_block_sizes are seams for tests on host pointers: the code lengths (at most max_bits) of
+ * n_sym frequencies, with the forced pair where fewer than two are used; the three sizes in bits of one block (n <= CTO_BGZF_PAYLOAD)
+ * and its token histogram (286 literal/length symbols, then 30 distance symbols).
+ * cto_bam_mix_ex is cto_bam_mix with the coder of the output's blocks chosen: 0 zlib level 6 (cto_bam_mix's bytes), 1 this coder on
+ * the device, 2 its host restatement on host_threads threads.  1 and 2 write the same bytes; block cuts, inflated content and the
+ * .bai rules are those of 0.  With where = 1 and deflate = 1 a window's merged stream stays on the device behind the bytes the
+ * previous window left over, and only the compressed blocks come down; dstats (may be NULL) sums the coder's calls.
+ * ---------------------------------------------------------------------------------------------- */
+#define CTO_BGZF_PAYLOAD 0xff00
+typedef struct cto_deflate_stats { int64_t n_blocks, in_bytes, out_bytes, stored, fixed, dynamic; double ms_kernels; } cto_deflate_stats;
+int cto_bgzf_deflate(const void* in, int64_t n, int where /* 0 device, 1 host */, int host_threads, void* out, uint32_t* sizes, void* stream,
+                     cto_deflate_stats* stats);
+int cto_deflate_code_lengths(const uint32_t* freq, int n_sym, int max_bits, int where /* 0 device, 1 host */, uint8_t* len);
+int cto_deflate_block_sizes(const uint8_t* block, int n, int where /* 0 device, 1 host */, int64_t bits[3] /* stored, fixed, dynamic */,
+                            uint32_t hist[316]);
+int cto_bam_mix_ex(const char* tumor_path, const char* tumor_bai, const char* normal_path, const char* normal_bai,
+                   const char* ctg_name /* or NULL */, int m_tumor, int m_normal /* thousandths, 0 .. 1000 */, uint32_t seed,
+                   const char* out_path, int where /* 0 host, 1 device */, int host_threads, void* stream, cto_contam_stats* stats,
+                   int deflate /* 0 zlib, 1 device coder, 2 its host restatement */, cto_deflate_stats* dstats);
+
+/* ----------------------------------------------------------------------------------------------
  * Germline genotypes (csrc/germline.hip): the window distances of the reference's predictGermlineGenotypes
  * (src/verdict/predict_germline_genotypes.py:70-154, step 4 of the Verdict chain), over runs of undecided probes.
  *   c               the mirrored BAFs min(baf, 1 - baf) of the undecided probes, run after run, fp64 on the host; no NaN
